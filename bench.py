@@ -2,7 +2,7 @@
 """Headline benchmark: 6 h forecast sample-steps / second of the Swift-B sCM 1-step sampler
 (BASELINE.json configs[1]: 128x256x69 synthetic ERA5-shaped fields, bf16 GEMM operands).
 
-  python bench.py --gpus N --steps K --warmup W [--batch B] [--dtype bf16|f32]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--dtype bf16|f32] [--dump-outputs DIR] [--full]
   python bench.py --gpus N --rollout 12x64x60           (BASELINE configs[3]: the north-star rollout, strong scaling)
 
 A "step" is one pass of the hot path over one batch of B (member, IC) units on every rank: draw the latent noise, one
@@ -19,18 +19,30 @@ per-step checksum all-gather and the barriers.  Launched bare (`python bench.py 
 starts the N ranks itself, before anything touches the GPU; under torch.distributed.run it is one of the ranks.  It
 exits non-zero when the process group's world size is not --gpus.
 
-Extra objects in the same JSON line:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given and prints the
+line.  Extra objects in the same JSON line:
   roofline        dominant kernel (w1 GEMM + fused SwiGLU, 42.7 % of all FLOPs): algorithmic FLOPs per launch / mean launch
                   time from HIP events recorded on the launch stream during the timed region
+  rccl, checksum, per_rank  the process group that ran, what it collected and each rank's split of the timed region
+
+and with --full (every leg below takes runs of its own; --no-extras drops hip_runtime and the N == 1 legs again):
+  hip_runtime     a captured memset replayed in a fresh child process
   attention_roofline  the fused to_qkv + window-attention kernel against the MFMA roofline over its fused FLOPs (two more
                   steps, outside the timed region)
-  rccl, checksum  the process group that ran and what it collected
+  rollout_<spec>  (N > 1) BASELINE configs[3] as a fixed job split over the ranks (strong scaling)
+  batch_sweep, config3_2s, rollout_12x8x60, variants, generate_e2e, training  (N == 1) other sizes, samplers, models and the
+                  training step
   parity_engine   (N == 1) the exact-fp32 engine -- the configuration that meets the 1e-4 tolerance -- on the same
                   workload: sample-steps/s, fraction of the fp32 matrix peak, its attention kernel's MFMA fraction
   bf16_vs_fp32    (N == 1) relative L2 distance of the bf16 engine's state from the fp32 engine's after 1, 10 and 60
                   autoregressive steps on the same units and noise
   cpu_baseline    (N == 1) the CPU oracle -- a plain-PyTorch fp32 restatement of the reference, pinned to it by
                   tests/golden -- timed on the host cores for a bounded sample of the same workload
+
+--dump-outputs DIR writes what the timed path hands its caller after its last timed step, before any --full leg runs: the
+all-gathered per-unit checksums (unit_checksum.npy, fp64) and a fixed, seeded sample of rank 0's standardised and physical
+states (state_std.npy, state_phys.npy, fp32; whole arrays when they are small enough).  Weights, states, forcings and noise
+are seeded, so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -65,7 +77,12 @@ def parse_args():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "bf16x3"],
                     help="bf16 = BASELINE configs[1]'s dtype (default); f32 = exact-fp32 engine; bf16x3 = fp32-grade split-bf16 engine")
     ap.add_argument("--cpu-steps", type=int, default=3, help="samples of the CPU baseline, median reported (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip parity_engine / bf16_vs_fp32 / cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg as well (roofline, other sizes / precisions / samplers, rollouts, "
+                         "CPU baseline, training); a plain run does only the headline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip parity_engine / bf16_vs_fp32 / cpu_baseline legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (fp32 / fp64, a fixed sample of large arrays)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the WHOLE step (noise draw included) as one HIP graph (pays off below ~8 units per step)")
     ap.add_argument("--solver", default="scm", choices=["scm", "2s", "dpm"],
@@ -81,6 +98,10 @@ def parse_args():
         ap.error(f"--batch must be in 1..{MAX_UNITS} (SWIFTK_MAX_UNITS: one swiftk_swinv2_forward call takes at most that many units)")
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.rollout:
+        ap.error("--dump-outputs applies to the timed steps, not to --rollout")
     return a
 
 
@@ -316,6 +337,28 @@ def unit_inputs(units, dev, slabs: int = 1):
     return X, F
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept per state array: 2 x 16 MB of fp32, inside the 64 MB bound of a dump
+
+
+def dump_outputs(out_dir, X, phys, ck_all, seed: int = 0):
+    """--dump-outputs: the last step's per-unit checksums (all ranks) and rank 0's standardised / physical states, as .npy.  A
+    state larger than DUMP_SAMPLE elements is sampled at the same seeded, sorted flat indices for both arrays (the indices depend
+    only on the state's shape, so two runs with the same arguments sample the same elements)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = X.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(X.device)
+    for name, t in (("state_std", X), ("state_phys", phys)):
+        v = t.reshape(-1).index_select(0, idx) if idx is not None else t
+        np.save(os.path.join(out_dir, name + ".npy"), v.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "unit_checksum.npy"), ck_all.double().cpu().numpy())
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-worker":  # child of cpu_baseline_parallel: never touches the GPU
         return cpu_worker(int(sys.argv[2]), sys.argv[3], int(sys.argv[4]))
@@ -360,6 +403,7 @@ def main():
     # (kernel A/B knobs: SWIFTK_TUNE=key:value,... is applied by _lib.lib() when the library is loaded)
     dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "bf16x3": "bf16x3"}[a.dtype]
     B, K, W = a.batch, a.steps, a.warmup
+    extras = a.full and not a.no_extras
 
     net, state = build_net(dev, rank, grouped)
     ds = SyntheticERA5Dataset([f"v{i}" for i in range(NV)], [f"f{i}" for i in range(NF)], img_resolution=IMG, length=64,
@@ -384,7 +428,7 @@ def main():
     # what this process's HIP runtime does with a captured memset: recorded beside the numbers; the library itself
     # never captures one
     hip_rt = None
-    if rank == 0 and not a.no_extras:
+    if rank == 0 and extras:
         try:  # (in a fresh child process: whether the stale slot is overwritten within a short probe depends on the process's state --
             # a fresh interpreter shows the HIP 7.0.x bug in a quarter of the replays, this one, with its pools warm, often in none)
             code = ("import json, sys; sys.path.insert(0, %r); from swift_amd.graphs import memset_node_probe; "
@@ -509,10 +553,12 @@ def main():
         raise SystemExit("non-finite forecast state")
     ck_host = ck_all.cpu()
     ck_steps_host = ck_steps[W:W + K].cpu()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, X, phys, ck_all)
     # second roofline leg, outside the timed region: the window-attention kernel (north_star's named kernel) over two
     # more steps, HIP events on its launch stream
     att_ms, att_n = ctypes.c_double(0), ctypes.c_int64(0)
-    if a.dtype == "bf16" and not a.graph:
+    if a.full and a.dtype == "bf16" and not a.graph:
         lib.swiftk_profile_gemm(_lib.PROF_ATTENTION, 0)
         for _ in range(2):
             step()
@@ -527,7 +573,7 @@ def main():
 
     strong = None
     strong_spec = os.environ.get("SWIFTK_BENCH_STRONG", "12x64x60")  # (tests shrink the job; the key carries the spec)
-    if world > 1 and (not a.no_extras or "SWIFTK_BENCH_STRONG" in os.environ) and a.solver == "scm" and nsteps == 1:
+    if world > 1 and a.full and (extras or "SWIFTK_BENCH_STRONG" in os.environ) and a.solver == "scm" and nsteps == 1:
         # BASELINE configs[3] itself -- 12 members x 64 ICs x 60 steps, a FIXED job split over the ranks (strong scaling) -- beside
         # the weak-scaling headline, so that one driver invocation per N yields both curves
         import copy
@@ -640,7 +686,7 @@ def main():
                     "mfma_tflops": att_flop / att_s / 1e12, "mfma_frac": att_flop / att_s / PEAK_BF16,
                     "note": "arithmetic intensity 128 flop/B < ridge 312: the HBM roofline caps MFMA utilisation at 41 % in bf16; the "
                             "MFMA-bound regime is the fp32 engine's kernel (parity_engine.attention_mfma_frac)"}
-        if world == 1 and not a.no_extras and a.solver == "scm" and nsteps == 1:
+        if world == 1 and extras and a.solver == "scm" and nsteps == 1:
             for key, leg in (("batch_sweep", lambda: batch_sweep_leg(eng.net, ds, dev, X0, forc, units, dtype)),
                              ("config3_2s", lambda: config3_leg(eng.net, ds, dev, X0, forc, units, dtype)),
                              ("rollout_12x8x60", lambda: rollout_leg(a, eng, dev, B, sync)),
@@ -651,7 +697,7 @@ def main():
                     line[key] = leg()
                 except Exception as e:  # noqa: BLE001 -- a reported extra must not take the metric's line down
                     line[key] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not a.no_extras and a.cpu_steps > 0:
+        if world == 1 and extras and a.cpu_steps > 0:
             cb = cpu_baseline(state, a.cpu_steps)
             # the metric is a throughput over independent units: several oracle forecasts side by side use the host better than one
             # forecast on many threads (128 threads on one forecast are 2.8 x SLOWER than 32: NUMA).  The larger figure is the baseline.
@@ -666,7 +712,7 @@ def main():
                 cb["parallel"] = par
             line["cpu_baseline"] = cb
             line["vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
-        if world == 1 and not a.no_extras and a.solver == "scm" and nsteps == 1:
+        if world == 1 and extras and a.solver == "scm" and nsteps == 1:
             # the children plan their resident activations around what other processes hold: hand the forecast path's
             # buffers (workspace for 96 units, states, engines) back first
             import gc

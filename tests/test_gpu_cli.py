@@ -150,7 +150,7 @@ def test_bench_contract_line(tmp_path):
     e = dict(os.environ, PYTHONPATH=ROOT)
     e.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-steps", "0",
-                        "--batch", "16"], cwd=str(tmp_path), env=e, capture_output=True, text=True, timeout=900)
+                        "--batch", "16", "--full"], cwd=str(tmp_path), env=e, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -213,7 +213,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
         pytest.skip("no GPU")
     e = dict(os.environ, PYTHONPATH=ROOT, SWIFTK_ALLOW_SHARED_GPU="1", SWIFTK_DIST_BACKEND="gloo", SWIFTK_BENCH_STRONG="2x3x2")
     e.pop("WORLD_SIZE", None)
-    common = ["--steps", "3", "--warmup", "1", "--batch", "4", "--no-extras"]
+    common = ["--steps", "3", "--warmup", "1", "--batch", "4", "--full", "--no-extras"]
     out = {}
     for n in (1, 2):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + common, cwd=str(tmp_path), env=e,
@@ -238,6 +238,43 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     st = d2["rollout_2x3x2"]
     assert "rollout_2x3x2" not in d1 and st["scaling"] == "strong" and st["value"] > 0 and st["config"]["units"] == 6
     assert st["per_rank"]["units"] == [3.0, 3.0] and len(st["per_rank"]["barrier_wait_ms"]) == 2
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run carries the headline keys and the timed region's GEMM roofline but none of the --full legs;
+    --dump-outputs writes the last timed step's per-unit checksums (the line's own) and a fixed sample of the state, bit for bit
+    the same in two runs with the same arguments."""
+    import json
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    e = dict(os.environ, PYTHONPATH=ROOT)
+    e.pop("WORLD_SIZE", None)
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"dump{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(out)], cwd=str(tmp_path), env=e, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+        assert d["value"] == pytest.approx(4 * 3 / (d["ms_per_step"] * 3 / 1e3), rel=1e-3)
+        assert "roofline" in d and d["hip_runtime"] is None
+        for k in ("attention_roofline", "batch_sweep", "config3_2s", "rollout_12x8x60", "variants", "parity_engine", "bf16_vs_fp32",
+                  "cpu_baseline", "generate_e2e", "training"):
+            assert k not in d, k
+        files = sorted(os.listdir(out))
+        assert files == ["state_phys.npy", "state_std.npy", "unit_checksum.npy"], files
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        arrs = {f[:-4]: np.load(out / f) for f in files}
+        assert arrs["unit_checksum"].dtype == np.float64 and arrs["unit_checksum"].tolist() == d["checksum"]["last_step_first_units"]
+        for k in ("state_std", "state_phys"):
+            assert arrs[k].dtype == np.float32 and arrs[k].shape == (1 << 22,) and np.isfinite(arrs[k]).all()
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 @pytest.mark.timeout(900)

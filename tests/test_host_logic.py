@@ -759,6 +759,18 @@ def test_bench_launcher_contract_without_gpu():
     assert p.returncode == 2 and "SWIFTK_MAX_UNITS" in p.stderr
 
 
+def test_bench_step_and_dump_arguments_without_gpu():
+    """--steps sets the number of timed steps, so it must be at least one; --dump-outputs belongs to the timed steps, not to the
+    --rollout mode; both are refused before anything is imported or touches the GPU."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    bench = os.path.join(ROOT, "bench.py")
+    p = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, env=env, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    for args in (["--steps", "0"], ["--warmup", "-1"], ["--rollout", "2x2x2", "--dump-outputs", "out"]):
+        p = subprocess.run([sys.executable, bench] + args, capture_output=True, text=True, env=env, timeout=120)
+        assert p.returncode == 2 and ("--steps" in p.stderr or "--dump-outputs" in p.stderr) and not p.stdout.strip(), args
+
+
 def test_index_streams_vs_reference_golden():
     """``InfiniteSampler`` / ``DeltaBatchSampler`` emit the reference's index stream (data/samplers.py:9-85; fixture made by
     the reference's own samplers, tools/make_golden.py::fx_index_streams) -- several laps, rank strides, offsets, no-shuffle."""
