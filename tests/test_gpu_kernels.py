@@ -237,16 +237,17 @@ def test_modnorm_residual(dev, dt, rps):
     assert (xc[:, d:].float() == 7.0).all()  # pad columns untouched
 
 
-@pytest.mark.parametrize("lo_bits", [8, 16])
-@pytest.mark.parametrize("rps", [512, 48])
-def test_modnorm_residual_pair(dev, rps, lo_bits):
+# d: Swift-B, and the 468M / 664M widths (1280: the packed kernel's other row width; 1536: the row-per-wave kernel)
+@pytest.mark.parametrize("rps,lo_bits,d", [pytest.param(r, b, d_, id=f"{r}-{b}" if d_ == 1056 else f"{r}-{b}-d{d_}")
+                                           for d_ in (1056, 1280, 1536) for r in (512, 48) for b in (8, 16)])
+def test_modnorm_residual_pair(dev, rps, lo_bits, d):
     """The bf16 engine's residual stream as a pair -- hi = bf16(x) plus a bf16 or an 8-bit low part (swiftk_split_pair,
     swiftk_modnorm_residual_pair): the split is exact bf16 arithmetic (bit-equal to torch), the update is the oracle's
     ModulatedNorm + residual (swinv2.py:83-86, 211-212) on the value the pair stands for, stored back to 2^-17 relative, and hi
     is what a bf16 cast of the new x gives."""
     from oracle.swinv2 import modulated_norm
     from swift_amd import ops
-    B, d = 3, 1056
+    B = 3
     M = B * rps
     y, x = rnd((M, d), 12, 2.0) + 0.5, rnd((M, d), 13)
     p = {"n.norm.weight": 1 + 0.1 * rnd((d,), 14), "n.norm.bias": 0.1 * rnd((d,), 15),
@@ -266,8 +267,8 @@ def test_modnorm_residual_pair(dev, rps, lo_bits):
     yd = to_dt(y, torch.bfloat16, dev)
     hi[:, d:] = 7.0
     if lo_bits == 8:
-        # d = 1056 with the 8-bit low part runs the PACKED kernel (four rows per wave pass, no idle lanes); the row-per-wave
-        # form of the same arithmetic (tuning key 6 bit 2) must agree with it bit for bit
+        # d = 1056 / 1280 with the 8-bit low part run the PACKED kernel (four rows per wave pass, no idle lanes); the row-per-wave
+        # form of the same arithmetic (tuning key 6 bit 2; at d = 1536 both settings run it) must agree with it
         from swift_amd import _lib
         h2, l2 = hi.clone(), lo.clone()
         _lib.lib().swiftk_set_tuning(6, 7)
@@ -281,7 +282,7 @@ def test_modnorm_residual_pair(dev, rps, lo_bits):
     ref = x_in.view(B, rps, d) + modulated_norm(yd.float().cpu().view(B, rps, d), lat, p, "n.")
     got = ops.pair_value(hi, lo, d).cpu()
     e = rel_l2(got, ref.view(M, d))
-    print(f"pair ModulatedNorm (rows per sample {rps}, {lo_bits}-bit low part): pair value vs oracle rel-L2 {e:.2e}")
+    print(f"pair ModulatedNorm (d {d}, rows per sample {rps}, {lo_bits}-bit low part): pair value vs oracle rel-L2 {e:.2e}")
     assert e < 1e-5
     assert float((got - ref.view(M, d)).abs().max() / ref.abs().max()) < 2.0 ** -15
     # hi is the bf16 operand of the new x: lo stays within half an ulp of hi; re-rounding hi + lo differs only where lo rounded
@@ -332,14 +333,17 @@ def test_unit_noise_vs_oracle(dev):
     assert float(big.abs().max()) < 6.5 and torch.isfinite(big).all()
 
 
-@pytest.mark.parametrize("lo_bits", [8, 16])
-def test_modnorm_residual_pair_from_splitk_slabs(dev, lo_bits):
+# d: Swift-B; the 468M width (its one-unit step also runs split-K + the halves norm)
+@pytest.mark.parametrize("lo_bits,d", [pytest.param(b, d_, id=f"{b}" if d_ == 1056 else f"{b}-d{d_}") for d_ in (1056, 1280) for b in (8, 16)])
+def test_modnorm_residual_pair_from_splitk_slabs(dev, lo_bits, d):
     """Round 4, one unit per step: wo / w2 run as two k-ranges into fp32 slabs (swiftk_gemm_splitk) and the pair-form norm kernel
     sums them on its way (swiftk_modnorm_residual_pair_slabs).  Slabs from the real split-K GEMM; against the oracle's
-    ModulatedNorm on the fp64 product, and against the one-launch GEMM + bf16 y path (which rounds y to bf16 first)."""
+    ModulatedNorm on the fp64 product, and against the one-launch GEMM + bf16 y path (which rounds y to bf16 first).  With bf16 slabs
+    and the 8-bit low part, also the packed halves norm the forward runs behind them (swiftk_modnorm_residual_pair_halves_bf16,
+    tail = NULL)."""
     from oracle.swinv2 import modulated_norm
     from swift_amd import _lib, ops
-    B, rps, d, K = 2, 256, 1056, 2816
+    B, rps, K = 2, 256, 2816
     M = B * rps
     a, w, x = rnd((M, K), 51), rnd((d, K), 52, 0.03), rnd((M, d), 53)
     ad, wd = to_dt(a, torch.bfloat16, dev), to_dt(w, torch.bfloat16, dev)
@@ -376,14 +380,38 @@ def test_modnorm_residual_pair_from_splitk_slabs(dev, lo_bits):
     e_bf = rel_l2(ops.pair_value(hi3, lo3, d).cpu(), got)
     print(f"  bf16 slabs vs fp32 slabs {e_bf:.2e} (one launch, bf16 y: {e_one:.2e})")
     assert e_bf < 3e-3 and e_bf < 2.0 * e_one
+    if lo_bits == 8:
+        # the packed halves norm, every row two slabs: bit-equal to the one-y kernel on bf16(slab 0 + slab 1), and the oracle's
+        # ModulatedNorm on that y (fp64) to 1e-5
+        hi5, lo5 = ops.split_pair(x.to(dev), ld, 8)
+        hi6, lo6 = hi5.clone(), lo5.clone()
+        gam, bet = p["n.norm.weight"].to(dev), p["n.norm.bias"].to(dev)
+        _lib.check(_lib.lib().swiftk_modnorm_residual_pair_halves_bf16(sb.data_ptr(), M * d, None, hi5.data_ptr(), ld, lo5.data_ptr(),
+                                                                       gam.data_ptr(), bet.data_ptr(), mod.data_ptr(), 2 * d, M, d, rps,
+                                                                       1e-6, torch.cuda.current_stream().cuda_stream),
+                   "halves norm, tail = NULL")
+        ysum = (sb[0].float() + sb[1].float()).bfloat16()
+        ops.modnorm_residual_pair(ysum, hi6, lo6, gam, bet, mod, rps, d)
+        torch.cuda.synchronize()
+        assert torch.equal(hi5, hi6) and torch.equal(lo5, lo6)
+        ref_h = (x_in.double().view(B, rps, d) + modulated_norm(ysum.cpu().double().view(B, rps, d), lat.double(),
+                                                                {k: v.double() for k, v in p.items()}, "n."))
+        e_h = rel_l2(ops.pair_value(hi5, lo5, d).cpu(), ref_h.view(M, d))
+        print(f"  packed halves norm (tail = NULL, d {d}): bit-equal to the one-y kernel; vs the oracle on bf16(slab 0 + slab 1) {e_h:.2e}")
+        assert e_h < 1e-5
 
 
-@pytest.mark.parametrize("units,K,ldk", [(3, 1056, 1088), (4, 2816, 2816), (6, 1056, 1088), (4, 1056, 1088)])
+@pytest.mark.parametrize("units,K,ldk", [(3, 1056, 1088), (4, 2816, 2816), (6, 1056, 1088), (4, 1056, 1088),
+                                         # the halves norm as two launches (one-y kernel below rows_from, two-slab form from it on):
+                                         # rows_from on a unit boundary (9), inside a unit (11, 12, 14)
+                                         (9, 1056, 1088), (9, 2816, 2816), (11, 1056, 1088), (11, 2816, 2816),
+                                         (12, 1056, 1088), (12, 2816, 2816), (14, 1056, 1088), (14, 2816, 2816)])
 def test_gemm_tail_split_and_halves_norm(dev, units, K, ldk):
     """Round 6, small batches: wo / w2 with the persistent walk's LAST round as two k-halves (swiftk_gemm_tail_split_bf16) and the
     packed pair norm that adds the halves (swiftk_modnorm_residual_pair_halves_bf16).  Whole tiles are bit-equal to the plain GEMM and
     leave slab 1 alone, split tiles sum to the product; the norm reads slab 1 under the split tiles only and equals the one-y kernel
-    on bf16(slab 0 + slab 1) bit for bit; shapes without such a round are refused."""
+    on bf16(slab 0 + slab 1) bit for bit -- on the GEMM's own walk description and on hand-made ones (rows_from inside a sample, on
+    a sample boundary, 0; a group height that leaves a ragged last group); shapes without such a round are refused."""
     import ctypes
     from swift_amd import _lib, ops
     L = _lib.lib()
@@ -436,6 +464,34 @@ def test_gemm_tail_split_and_halves_norm(dev, units, K, ldk):
     torch.cuda.synchronize()
     assert not torch.isnan(ops.pair_value(hi, lo, d)).any()
     assert torch.equal(hi, hi2) and torch.equal(lo, lo2)
+    # hand-made walk descriptions (rows_from, tail_from, gm) on random slabs, slab 1 NaN wherever the description has no split tile:
+    # the first launch must stop and the second start exactly at rows_from, and the second must derive every row's sample and tile
+    # (group of gm tile rows, ragged last group when gm does not divide the tile rows) from the description alone
+    cdiv = lambda a, b: -(-a // b)
+
+    def first_split_tile(row, gm_):  # a tail_from whose split tiles all sit in tile rows from `row` on (five tiles into a group)
+        return cdiv(cdiv(row, 256), gm_) * gm_ * ntn + 5
+    inside = rps + rps // 2 + 48  # inside sample 1, not on a tile row either; gm 5 leaves a ragged last group at every unit count here
+    for rf, gm_, tf in ((inside, 5, first_split_tile(inside, 5)), ((units - 1) * rps, 4, first_split_tile((units - 1) * rps, 4)),
+                        (0, 8, tiles // 2 + 1)):
+        assert rf % 16 == 0 and 0 < tf < tiles
+        idx_ = (tm // gm_) * gm_ * ntn + tn * torch.clamp(ntm - (tm // gm_) * gm_, max=gm_) + (tm - (tm // gm_) * gm_)
+        sel_ = (idx_ >= tf).to(dev)[:, None, :, None].expand(ntm, 256, ntn, 352)
+        assert not bool(sel_[: cdiv(rf, 256)].any()) and bool(sel_.any()) and not bool(sel_.all())
+        ys = torch.randn(2, M, d, generator=g, device=dev).bfloat16()
+        ys[1].view(ntm, 256, ntn, 352)[~sel_] = float("nan")
+        hi5, lo5 = ops.split_pair(x, ld, 8)
+        hi6, lo6 = hi5.clone(), lo5.clone()
+        desc = (ctypes.c_int64 * 3)(rf, tf, gm_)
+        _lib.check(L.swiftk_modnorm_residual_pair_halves_bf16(ys.data_ptr(), M * d, desc, hi5.data_ptr(), ld, lo5.data_ptr(), gam.data_ptr(),
+                                                              bet.data_ptr(), mod.data_ptr(), 2 * d, M, d, rps, 1e-6, st), "halves norm, hand-made")
+        y0_, y1_ = ys[0].view(ntm, 256, ntn, 352), ys[1].view(ntm, 256, ntn, 352)
+        ops.modnorm_residual_pair(torch.where(sel_, (y0_.float() + y1_.float()).bfloat16(), y0_).reshape(M, d).contiguous(), hi6, lo6, gam,
+                                  bet, mod, rps, d)
+        torch.cuda.synchronize()
+        print(f"  hand-made description rows_from {rf} (sample {rf // rps}, {'on a boundary' if rf % rps == 0 else 'inside'}), "
+              f"tail_from {tf}, gm {gm_}: bit-equal {torch.equal(hi5, hi6) and torch.equal(lo5, lo6)}")
+        assert torch.equal(hi5, hi6) and torch.equal(lo5, lo6)
     # tail = NULL: two halves everywhere (behind swiftk_gemm_splitk_bf16)
     both = torch.randn(2, M, d, generator=g, device=dev).bfloat16()
     hi3, lo3 = ops.split_pair(x, ld, 8)
@@ -444,8 +500,9 @@ def test_gemm_tail_split_and_halves_norm(dev, units, K, ldk):
                                                           bet.data_ptr(), mod.data_ptr(), 2 * d, M, d, rps, 1e-6, st), "halves norm, all rows")
     ops.modnorm_residual_pair((both[0].float() + both[1].float()).bfloat16(), hi4, lo4, gam, bet, mod, rps, d)
     assert torch.equal(hi3, hi4) and torch.equal(lo3, lo4)
-    # no such round: two units (192 tiles: one partly filled round), five units (480: a last round of 224 > 128), eight (768 = 3 x 256)
-    for u in (2, 5, 8):
+    # no such round: two units (192 tiles: one partly filled round), five units (480: a last round of 224 > 128), eight (768 = 3 x 256),
+    # ten (960: a last round of 192), thirteen (1248: 224)
+    for u in (2, 5, 8, 10, 13):
         Mu = u * rps
         au, su = torch.zeros(Mu, ldk, dtype=torch.bfloat16, device=dev), torch.empty(2, Mu, d, dtype=torch.bfloat16, device=dev)
         assert L.swiftk_gemm_tail_split_bf16(au.data_ptr(), ldk, w.data_ptr(), ldk, su.data_ptr(), d, Mu * d, Mu, d, K, tail, st) == -2  # SWIFTK_ESHAPE

@@ -103,41 +103,222 @@ def test_forward_vs_reference_golden(dev):
         assert ev < BF16_EMU_TOL and not torch.equal(yv, yb)
 
 
-@pytest.mark.parametrize("units", [3, 4, 6])
-def test_forward_small_batch_tail_split(dev, units):
-    """Round 6: at 3 / 4 / 6 units per step wo / w2 leave the persistent walk a last round that is at most half full; the engine runs
-    that round's tiles as two k-halves (swiftk_gemm_tail_split_bf16 + swiftk_modnorm_residual_pair_halves_bf16, tuning key 29 bit 0).
-    Same network, same inputs, with and without: equal up to the halves' extra bf16 rounding; and a step is repeatable."""
+# unit-count sweep: one depth-2 Swift-B-width net on the full grid, a bank of K units, every batch-size form of the dispatch
+SWEEP_K = 7  # bank units; coprime to the slot step, so neighbouring slots differ and every batch above K repeats a unit
+SWEEP_B = (1, 2, 3, 4, 5, 6, 9, 11, 12, 14, 16, 17)
+UNIT_ROWS = 128 // 2 * 256 // 2  # tokens per unit on the full grid: 8192 rows = 32 tile rows of the 256 x 352 GEMM tiles
+# bf16 engine, one unit's output against the bf16-emulating oracle (depth 2, full grid), per slot, in units of that unit's noise floor
+# (the distance between the two admissible emulations, row-max offset and offset 0: 1.21e-2 .. 1.25e-2 for the bank).  Measured on the
+# MI355X: the plain form (whole-K wo / w2, the oracle's own rounding points) 0.85 .. 0.87 x the floor from the nearer emulation; the
+# tail / split-K forms, whose halves are rounded to bf16 before their sum is, 0.95 .. 1.16 x; every form at most 1.21 x from the
+# further one.  What a defect of these forms would cost, computed on the CPU with the emulating oracle: layer 0's wo missing one 32-wide
+# k-block in just the rows a three-unit batch splits (a quarter of bank unit 2 and a twelfth more) moves that unit 1.1e-1 = 9 x its
+# floor, 7 x the split bar; in every row of a unit 1.9e-1.
+SWEEP_EMU_PLAIN = 1.0   # x floor, nearer emulation, plain-form slots
+SWEEP_EMU_SPLIT = 1.3   # x floor, nearer emulation, slots with rows under split tiles / split-K slabs
+SWEEP_EMU_ANY = 1.4     # x floor, further emulation, every slot
+SWEEP_TAIL_VS_PLAIN = 1.3  # x floor: a unit in a tail / split-K slot against the same unit in the plain form (measured 0.73 .. 1.12 x)
+SWEEP_SPLIT_OVER_PLAIN = 1.5  # a split unit's distance to the emulation over its plain form's (measured 1.06 .. 1.35: the extra rounding)
+
+
+@pytest.fixture(scope="module")
+def sweep(dev):
+    """The net, the bank of units and the CPU oracle's outputs per bank unit (fp32; bf16 emulation with the row-max offset and with
+    offset 0), moved to the device once.  The oracle is per-sample independent: its cost does not grow with the batch sizes swept."""
+    from oracle.swinv2 import swinv2_forward
+    net, onet = build(dict(SWIFTB, depth=2), 5, dev)
+    K = SWEEP_K
+    x = det_normal((K, 141, 128, 256), 9, "bank-x")
+    t = torch.tensor([0.2, 1.4, 0.55, 0.9, 1.15, 0.35, 0.7])
+    aux = torch.tensor([[0.6], [1.2], [2.4], [0.3], [0.9], [1.8], [0.45]])
+    refs = {}
+    with torch.no_grad():
+        for name, emu in (("fp32", False), ("emu", True), ("emu0", "offset0")):
+            refs[name] = torch.cat([swinv2_forward(onet.cfg, onet.p, x[k:k + 1], t[k:k + 1], auxiliary=aux[k:k + 1], emulate_bf16=emu)
+                                    for k in range(K)], 0).to(dev)
+    return dict(net=net, x=x.to(dev), t=t.to(dev), aux=aux.to(dev), **refs)
+
+
+def slot_dist(y, ref):
+    """Per-slot relative L2 distance [B] (fp64, on the device)."""
+    y, ref = y.double().flatten(1), ref.double().flatten(1)
+    return ((y - ref).norm(dim=1) / ref.norm(dim=1)).tolist()
+
+
+def tail_walk(B, dev):
+    """(rows_from, tail_from, gm) of wo / w2's walk at B units and, per unit, whether any of its rows sits under a split tile; None
+    when the walk leaves no last round to split (swiftk_gemm_tail_split_bf16 on zero operands of that M)."""
+    import ctypes
+    from swift_amd import _lib
+    M, d, K, ldk = B * UNIT_ROWS, 1056, 1056, 1088
+    a, w = torch.zeros(M, ldk, dtype=torch.bfloat16, device=dev), torch.zeros(d, ldk, dtype=torch.bfloat16, device=dev)
+    slabs = torch.empty(2, M, d, dtype=torch.bfloat16, device=dev)
+    tail = (ctypes.c_int64 * 3)(-1, -1, -1)
+    rc = _lib.lib().swiftk_gemm_tail_split_bf16(a.data_ptr(), ldk, w.data_ptr(), ldk, slabs.data_ptr(), d, M * d, M, d, K, tail,
+                                                torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    if rc == -2:  # SWIFTK_ESHAPE
+        return None
+    _lib.check(rc, "swiftk_gemm_tail_split_bf16")
+    rows_from, tail_from, gm = tail[0], tail[1], tail[2]
+    ntm, ntn = M // 256, 3
+    tm, tn = torch.meshgrid(torch.arange(ntm), torch.arange(ntn), indexing="ij")
+    grp = tm // gm
+    idx = grp * gm * ntn + tn * torch.clamp(ntm - grp * gm, max=gm) + (tm - grp * gm)
+    split_rows = (idx >= tail_from).any(dim=1)  # per tile row
+    return rows_from, tail_from, gm, split_rows.view(B, UNIT_ROWS // 256).any(dim=1).tolist()
+
+
+def test_forward_unit_count_sweep_vs_oracle(dev, sweep):
+    """The forecast engine picks its wo / w2 + ModulatedNorm form from the number of units in the call (csrc/forward.hip): one unit
+    split-K into two bf16 slabs + the packed halves norm; 3, 4, 6, 9, 11, 12, 14, 17 the persistent walk's last round as k-halves
+    (swiftk_gemm_tail_split_bf16) + the halves norm as two launches, split at rows_from -- on a unit boundary at 9 and 17, inside a
+    unit at the others; 2, 5, 16 the plain GEMM + pair norm; from 16 units on the modulation Linears run on the fp32 MFMA GEMM.
+    Every batch is a different arrangement of the bank's units (slot j = bank[(s + 3 j) mod 7]); every assertion is per slot, against
+    that unit's oracle output.
+
+    fp32 / bf16x3: within FP32_TOL of the fp32 oracle; a unit's output bit-identical in every slot of every batch on the same side of
+    the 16-unit switch, and within 2e-6 (exact engine) / 1e-5 (split engine) across it (see the end of the test).
+    bf16: within the calibrated bars of the two bf16 emulations; a unit whose rows meet no split tile (and every unit of a plain-form
+    run) bit-identical to its plain-form output in every batch on the same side of the switch; a unit in a tail / split-K slot within
+    SWEEP_TAIL_VS_PLAIN of its plain form, and no further from the emulation than SWEEP_SPLIT_OVER_PLAIN x the plain form is.  The
+    reference forms stay covered: key 29 = 0 (plain at the tail counts, the generic two-slab norm behind the split-K) and key 14 = 0
+    (whole tiles at one unit); with the ping-pong loop off (key 20 = 0) the tail counts fall back to whole tiles bit for bit; a tail step is repeatable."""
     from swift_amd import _lib
     L = _lib.lib()
-    net, _ = build(dict(SWIFTB, depth=2), 5, dev)
-    x = det_normal((units, 141, 128, 256), 9, "x").to(dev)
-    t = torch.linspace(0.2, 1.4, units).to(dev)
-    aux = torch.full((units, 1), 0.6).to(dev)
+    net, K = sweep["net"], SWEEP_K
+    fails = []
 
-    def run():
-        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-            return net.model(x, t, auxiliary=aux).float()
+    def check(ok, what):
+        if not ok:
+            fails.append(what)
 
-    y_tail, y_again = run(), run()
-    old = L.swiftk_get_tuning(29)
-    L.swiftk_set_tuning(29, old & ~1)
-    try:
-        y_plain = run()
-    finally:
-        L.swiftk_set_tuning(29, old)
-    # with the GEMM's ping-pong loop switched off (tuning key 20) the k-half walk does not exist: the engine must fall back to whole
-    # tiles by itself -- and that loop is bit-equal to the ping-pong one, so the result is the whole-tile result
-    L.swiftk_set_tuning(20, 0)
-    try:
-        y_fallback = run()
-    finally:
-        L.swiftk_set_tuning(20, 1)
-    assert torch.equal(y_fallback, y_plain)
-    e = rel_l2(y_tail.cpu(), y_plain.cpu())
-    print(f"forward, {units} units, depth 2: last round as k-halves vs whole tiles rel-L2 {e:.3e}")
-    assert torch.isfinite(y_tail).all() and torch.equal(y_tail, y_again)
-    assert e < 1e-2 and not torch.equal(y_tail, y_plain)  # (two bf16 forms of the same network: 5e-3 apart at depth 2; the other path did run)
+    def run(idx, engine, tune=()):
+        old = {k: L.swiftk_get_tuning(k) for k, _ in tune}
+        for k, v in tune:
+            L.swiftk_set_tuning(k, v)
+        try:
+            x, t, aux = sweep["x"][idx], sweep["t"][idx], sweep["aux"][idx]
+            with torch.no_grad():
+                if engine == "bf16":
+                    with torch.autocast("cuda", dtype=torch.bfloat16):
+                        return net.model(x, t, auxiliary=aux).float()
+                net.model.fp32_engine = "bf16x3" if engine == "bf16x3" else None
+                try:
+                    return net.model(x, t, auxiliary=aux)
+                finally:
+                    net.model.fp32_engine = None
+        finally:
+            for k, v in old.items():
+                L.swiftk_set_tuning(k, v)
+
+    def worst(name, B, e):
+        j = int(np.argmax(e))
+        print(f"  B {B:2d} {name:24s} worst slot {j:2d} (unit {idx[j]}): {e[j]:.3e}")
+
+    fp_ref = {}      # (engine, unit, B >= 16) -> the unit's output of the fp32-grade engine
+    plain_ref = {}   # (unit, B >= 16) -> the unit's bf16 output in the plain form
+    floor = slot_dist(sweep["emu0"], sweep["emu"])
+    print(f"unit-count sweep, depth 2, full grid: the two bf16 emulations from each other per bank unit "
+          f"{' '.join(f'{v:.2e}' for v in floor)}")
+    for B in SWEEP_B:
+        s = B % K
+        idx = [(s + 3 * j) % K for j in range(B)]
+        hi = B >= 16
+        walk = tail_walk(B, dev) if B > 1 else None
+        form = "split-K" if B == 1 else "tail" if walk else "plain"
+        split = [True] * B if B == 1 else walk[3] if walk else [False] * B
+        desc = ""
+        if walk:
+            rf = walk[0]
+            desc = (f"; rows_from {rf} in slot {rf // UNIT_ROWS} ({'on a unit boundary' if rf % UNIT_ROWS == 0 else 'inside the unit'}), "
+                    f"tail_from {walk[1]}, gm {walk[2]}")
+        print(f"B {B:2d}: units {idx}; form {form}; slots under split tiles {[j for j in range(B) if split[j]]}{desc}")
+        # ---- fp32-grade engines
+        for eng in ("fp32", "bf16x3"):
+            y = run(idx, eng)
+            e = slot_dist(y, sweep["fp32"][idx])
+            worst(f"{eng} vs fp32 oracle", B, e)
+            for j, u in enumerate(idx):
+                check(e[j] < FP32_TOL, f"B {B} {eng} slot {j} (unit {u}): {e[j]:.3e} from the fp32 oracle")
+                key = (eng, u, hi)
+                if key not in fp_ref:
+                    fp_ref[key] = y[j].clone()
+                elif not torch.equal(y[j], fp_ref[key]):
+                    check(False, f"B {B} {eng} slot {j} (unit {u}): not bit-equal to the same unit in an earlier batch "
+                                 f"({rel_l2(y[j], fp_ref[key]):.3e})")
+        # ---- bf16 engine
+        y = run(idx, "bf16")
+        er, e0 = slot_dist(y, sweep["emu"][idx]), slot_dist(y, sweep["emu0"][idx])
+        emin, emax = [min(a, b) for a, b in zip(er, e0)], [max(a, b) for a, b in zip(er, e0)]
+        worst("bf16 vs emulation (min)", B, emin)
+        worst("bf16 vs emulation (max)", B, emax)
+        forms = {form: (y, emin, emax)}
+        if form == "tail":
+            y_again = run(idx, "bf16")
+            check(bool(torch.isfinite(y).all()) and torch.equal(y, y_again), f"B {B} tail form: not finite or not repeatable")
+            forms["plain (key 29 = 0)"] = (run(idx, "bf16", ((29, 0),)),)
+            # with the GEMM's ping-pong loop off (key 20) the k-half walk does not exist: the engine falls back to whole tiles by itself,
+            # and that loop is bit-equal to the ping-pong one
+            y_fb = run(idx, "bf16", ((20, 0),))
+            check(torch.equal(y_fb, forms["plain (key 29 = 0)"][0]), f"B {B}: the key 20 = 0 fallback is not the whole-tile result")
+        elif form == "split-K":
+            forms["plain (key 14 = 0)"] = (run(idx, "bf16", ((14, 0),)),)
+            forms["two-slab norm (key 29 = 0)"] = (run(idx, "bf16", ((29, 0),)),)
+        for name in list(forms)[1:]:
+            yv = forms[name][0]
+            a_, b_ = slot_dist(yv, sweep["emu"][idx]), slot_dist(yv, sweep["emu0"][idx])
+            forms[name] = (yv, [min(p_, q_) for p_, q_ in zip(a_, b_)], [max(p_, q_) for p_, q_ in zip(a_, b_)])
+            worst(f"{name[:16]} vs emu (min)", B, forms[name][1])
+        for name, (yv, mn, mx) in forms.items():
+            for j, u in enumerate(idx):
+                bar = SWEEP_EMU_PLAIN if name.startswith("plain") or not split[j] else SWEEP_EMU_SPLIT
+                check(mn[j] < bar * floor[u] and mx[j] < SWEEP_EMU_ANY * floor[u],
+                      f"B {B} bf16 {name} slot {j} (unit {u}): {mn[j]:.3e} / {mx[j]:.3e} from the two emulations (floor {floor[u]:.3e})")
+        # plain-form outputs: bit-identical per unit across slots and batches (whole tiles are the plain GEMM's, tiles never straddle
+        # units, the fused to_qkv + attention kernel and the norms do not depend on the slot)
+        plain_name = form if form == "plain" else [n for n in forms if n.startswith("plain")][0]
+        for name, (yv, mn, mx) in forms.items():
+            for j, u in enumerate(idx):
+                if name == plain_name or (name == form and not split[j]):
+                    key = (u, hi)
+                    if key not in plain_ref:
+                        plain_ref[key] = yv[j].clone()
+                    elif not torch.equal(yv[j], plain_ref[key]):
+                        check(False, f"B {B} bf16 {name} slot {j} (unit {u}): not bit-equal to its plain form in another slot / batch "
+                                     f"({rel_l2(yv[j], plain_ref[key]):.3e})")
+        if form != "plain":
+            yp, pmin = forms[plain_name][0], forms[plain_name][1]
+            et = slot_dist(y, yp)
+            worst(f"{form} vs plain form", B, et)
+            check(not torch.equal(y, yp), f"B {B}: the {form} form did not run")
+            if form == "tail":  # (the batch as a whole: two bf16 forms of the same network, 5e-3 apart at three to six units)
+                e_all = rel_l2(y, yp)
+                check(e_all < 1e-2, f"B {B}: tail form vs plain form {e_all:.3e} for the batch")
+            for j, u in enumerate(idx):
+                if split[j]:
+                    check(et[j] < SWEEP_TAIL_VS_PLAIN * floor[u], f"B {B} slot {j} (unit {u}): {form} form {et[j]:.3e} from its plain form")
+                    check(emin[j] <= SWEEP_SPLIT_OVER_PLAIN * pmin[j], f"B {B} slot {j} (unit {u}): {form} form {emin[j]:.3e} from the "
+                                                                       f"emulation, plain form {pmin[j]:.3e}")
+                else:
+                    check(et[j] == 0.0, f"B {B} slot {j} (unit {u}): no split tile, yet {et[j]:.3e} from the plain form")
+    # Across the 16-unit switch of the modulation Linears: below 16 units swiftk_linear_small (VALU, one fp32 chain per output), from 16
+    # on swiftk_gemm (fp32 MFMA, its own k order) -- the same products summed in another order, a few fp32 ulps in the modulation
+    # vectors, which the cosine attention (logit scales up to 100) carries to the output.  Measured: exact engine 1.37 .. 1.41e-6, split
+    # engine 5.95 .. 6.07e-6 (its hi / lo operand split moves with the stream), bf16 engine 2.6e-3 (one flipped bf16 rounding spreads).
+    for (eng, u, h), v in fp_ref.items():
+        if not h and (eng, u, True) in fp_ref:
+            e = rel_l2(fp_ref[(eng, u, True)], v)
+            print(f"  {eng} unit {u}: below vs from 16 units {e:.3e}")
+            check(e <= (2e-6 if eng == "fp32" else 1e-5), f"{eng} unit {u}: {e:.3e} between below and from 16 units")
+    for (u, h), v in plain_ref.items():
+        if not h and (u, True) in plain_ref:
+            e = rel_l2(plain_ref[(u, True)], v)
+            print(f"  bf16 plain form, unit {u}: below vs from 16 units {e:.3e}")
+            check(e <= 5e-3, f"bf16 unit {u}: {e:.3e} between below and from 16 units")
+    for f_ in fails:
+        print("FAIL", f_)
+    assert not fails, f"{len(fails)} failures, first: {fails[0]}"
 
 
 @pytest.mark.parametrize("name,c", [
