@@ -217,6 +217,11 @@ int swiftk_gemm_bias_pos_pair(const void* A, int64_t lda, const void* W, int64_t
  */
 int swiftk_patchify(const float* src0, int c0, float s0, const float* src1, int c1, float s1, const float* src2, int c2,
                     float s2, void* A, int64_t lda, int B, int H, int W, int p1, int p2, int dtype, void* stream);
+/* The same with source 0 also multiplied by s0_per_sample[b] ([B] fp32 on the device; NULL = swiftk_patchify): EDM's
+ * c_in * x (reference models/precond.py:81-86, arg = c_in * x) read per sample without a host round trip. */
+int swiftk_patchify_scaled(const float* src0, int c0, float s0, const float* s0_per_sample, const float* src1, int c1, float s1,
+                           const float* src2, int c2, float s2, void* A, int64_t lda, int B, int H, int W, int p1, int p2,
+                           int dtype, void* stream);
 
 /*
  * out[b][c][y][x] = alpha[b] * xt[b][c][y][x] + beta[b] * tok[b][gy*gw+gx][(c*p1+i1)*p2+i2]
@@ -539,6 +544,15 @@ int swiftk_trigflow_prep(const float* x, const float* z, const float* t, float* 
 int swiftk_trigflow_loss(const float* F, const float* vt, const float* logvar, const float* w_var, const float* w_lat,
                          float* loss, float* dF, float* dlogvar, float sigma_data, int B, int C, int H, int W, float gscale,
                          void* stream);
+/* EDM (loss.py:95-114, replacing its `n = randn_like(x) * sigma`, `c_in * (x + n)` and the weighted squared error):
+ * prep writes the network input c_in,b (x + sigma_b z) from (x, z ~ N(0,1), sigma [B]); loss accumulates into *loss
+ * 1/(B H W) sum lambda_b w_var[c] w_lat[h] (D - x)^2 with D = c_skip,b x_n + c_out,b F and lambda = (s^2 + sd^2) / (s sd)^2,
+ * and writes dF = gscale * 2/(B H W) lambda_b c_out,b w_var w_lat (D - x) (dF may be NULL).  D - x is evaluated as
+ * c_out F + s / (s^2 + sd^2) (sd^2 z - s x), which keeps fp32 accuracy at small sigma. */
+int swiftk_edm_prep(const float* x, const float* z, const float* sigma, float* net_in, float sigma_data, int B,
+                    int64_t per_sample, void* stream);
+int swiftk_edm_loss(const float* F, const float* x, const float* z, const float* sigma, const float* w_var, const float* w_lat,
+                    float* loss, float* dF, float sigma_data, int B, int C, int H, int W, float gscale, void* stream);
 /* out = a[b]*x + c[b]*y (y may be NULL) ;  out = x + coef[channel]*y (x may be NULL) */
 int swiftk_axpby_per_sample(float* out, const float* a, const float* x, const float* c, const float* y, int B,
                             int64_t per_sample, void* stream);
@@ -681,6 +695,13 @@ int swiftk_swinv2_forward(const swiftk_model* m, const float* src0, int c0, floa
                           const float* src2, int c2, float s2, const float* t, const float* aux, const float* xt,
                           const float* alpha, const float* beta, float* out, float* logvar, int B, void* workspace,
                           int64_t workspace_bytes, void* stream);
+/* swiftk_swinv2_forward with source 0 also scaled per sample by s0_per_sample[b] ([B] fp32 device vector, NULL = none):
+ * EDMPrecond's arg = c_in * x (reference models/precond.py:81-86) inside the patch gather, so a forward at a device
+ * sigma tensor needs no host sync and no extra pass over x; D = c_skip x + c_out F is the alpha / beta epilogue. */
+int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* src0, int c0, float s0, const float* s0_per_sample,
+                                 const float* src1, int c1, float s1, const float* src2, int c2, float s2, const float* t,
+                                 const float* aux, const float* xt, const float* alpha, const float* beta, float* out,
+                                 float* logvar, int B, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

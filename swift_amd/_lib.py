@@ -77,6 +77,7 @@ _SIGS = {
     "swiftk_unit_noise": ([_p, _p, _p, _l, _i, _l, _i, _p], _i),
     "swiftk_counter_add": ([_p, _l, _p], _i),
     "swiftk_patchify": ([_p, _i, _f, _p, _i, _f, _p, _i, _f, _p, _l, _i, _i, _i, _i, _i, _i, _p], _i),
+    "swiftk_patchify_scaled": ([_p, _i, _f, _p, _p, _i, _f, _p, _i, _f, _p, _l, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_unpatchify_affine": ([_p, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_timestep_embed": ([_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p], _i),
     "swiftk_linear_small": ([_p, _l, _p, _l, _p, _p, _l, _i, _i, _i, _i, _p], _i),
@@ -128,6 +129,8 @@ _SIGS = {
     "swiftk_crps_loss": ([_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p], _i),
     "swiftk_trigflow_prep": ([_p, _p, _p, _p, _p, _f, _i, _l, _p], _i),
     "swiftk_trigflow_loss": ([_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _f, _p], _i),
+    "swiftk_edm_prep": ([_p, _p, _p, _p, _f, _i, _l, _p], _i),
+    "swiftk_edm_loss": ([_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _f, _p], _i),
     "swiftk_axpby_per_sample": ([_p, _p, _p, _p, _p, _i, _l, _p], _i),
     "swiftk_channel_axpy": ([_p, _p, _p, _p, _i, _i, _l, _p], _i),
     "swiftk_adamw_ema_step": ([_p, _i, _p, _p, _p, C.POINTER(OptHyper), _p], _i),
@@ -138,6 +141,8 @@ _SIGS = {
     "swiftk_workspace_bytes": ([C.POINTER(Model), _i], _l),
     "swiftk_swinv2_forward": ([C.POINTER(Model), _p, _i, _f, _p, _i, _f, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _i, _p,
                                _l, _p], _i),
+    "swiftk_swinv2_forward_scaled": ([C.POINTER(Model), _p, _i, _f, _p, _p, _i, _f, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _i,
+                                      _p, _l, _p], _i),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -689,6 +689,7 @@ struct PatchArgs {
     int c0[3];  // first channel of each source in the concatenated order
     int cn[3];
     float sc[3];
+    const float* sc0;  // optional [B] per-sample factor on source 0 (EDM's c_in), on top of sc[0]; nullptr = none
     int B, H, W, p1, p2, C, gh, gw;
     int64_t lda;
 };
@@ -711,6 +712,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(PatchArgs a, T* __restric
             const int s = c >= a.c0[2] ? 2 : (c >= a.c0[1] ? 1 : 0);
             const int64_t off = ((b * a.cn[s] + (c - a.c0[s])) * a.H + (gy * a.p1 + i1)) * a.W + gx * a.p2 + i2;
             val = a.src[s][off] * a.sc[s];
+            if (s == 0 && a.sc0) val *= a.sc0[b];
         }
         A[i] = elem<T>::from_f(val);
     }
@@ -733,7 +735,7 @@ __global__ __launch_bounds__(256) void patchify_tiled_kernel(PatchArgs a, T* __r
         const int s = c >= a.c0[2] ? 2 : (c >= a.c0[1] ? 1 : 0);
         const float* src = a.src[s] + (((int64_t)b * a.cn[s] + (c - a.c0[s])) * a.H + (gy * a.p1 + i1)) * a.W + gxb * 16 * a.p2 + 4 * q;
         float4 v = *reinterpret_cast<const float4*>(src);
-        const float sc = a.sc[s];
+        const float sc = (s == 0 && a.sc0) ? a.sc[0] * a.sc0[b] : a.sc[s];
         v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc;
         *reinterpret_cast<float4*>(ptile + r * rs + 4 * q) = v;
     }
@@ -1341,9 +1343,9 @@ extern "C" int swiftk_split_pair(const float* src, int64_t lds, void* hi, int64_
     return 0;
 }
 
-extern "C" int swiftk_patchify(const float* src0, int c0, float s0, const float* src1, int c1, float s1, const float* src2,
-                               int c2, float s2, void* A, int64_t lda, int B, int H, int W, int p1, int p2, int dtype,
-                               void* stream) {
+extern "C" int swiftk_patchify_scaled(const float* src0, int c0, float s0, const float* s0_per_sample, const float* src1, int c1,
+                                      float s1, const float* src2, int c2, float s2, void* A, int64_t lda, int B, int H, int W,
+                                      int p1, int p2, int dtype, void* stream) {
     if (!A || !src0 || c0 <= 0 || c1 < 0 || c2 < 0 || B <= 0 || p1 <= 0 || p2 <= 0) return SWIFTK_EINVAL;
     if ((c1 > 0 && !src1) || (c2 > 0 && !src2)) return SWIFTK_EINVAL;
     if (H % p1 || W % p2) return SWIFTK_ESHAPE;
@@ -1354,6 +1356,7 @@ extern "C" int swiftk_patchify(const float* src0, int c0, float s0, const float*
     if (c1 == 0) a.c0[1] = 1 << 30;
     if (c2 == 0) a.c0[2] = 1 << 30;
     a.sc[0] = s0; a.sc[1] = s1; a.sc[2] = s2;
+    a.sc0 = s0_per_sample;
     a.B = B; a.H = H; a.W = W; a.p1 = p1; a.p2 = p2; a.C = c0 + c1 + c2; a.gh = H / p1; a.gw = W / p2;
     a.lda = lda;
     if (lda < (int64_t)p1 * p2 * a.C) return SWIFTK_ESHAPE;
@@ -1381,6 +1384,12 @@ extern "C" int swiftk_patchify(const float* src0, int c0, float s0, const float*
         return SWIFTK_EINVAL;
     SWIFTK_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int swiftk_patchify(const float* src0, int c0, float s0, const float* src1, int c1, float s1, const float* src2,
+                               int c2, float s2, void* A, int64_t lda, int B, int H, int W, int p1, int p2, int dtype,
+                               void* stream) {
+    return swiftk_patchify_scaled(src0, c0, s0, nullptr, src1, c1, s1, src2, c2, s2, A, lda, B, H, W, p1, p2, dtype, stream);
 }
 
 extern "C" int swiftk_unpatchify_affine(const float* tok, int64_t ldt, const float* xt, const float* alpha,

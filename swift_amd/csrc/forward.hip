@@ -120,10 +120,10 @@ extern "C" int64_t swiftk_workspace_bytes(const swiftk_model* m, int B) {
     return make_layout(m, B).total;
 }
 
-extern "C" int swiftk_swinv2_forward(const swiftk_model* m, const float* src0, int c0, float s0, const float* src1, int c1,
-                                     float s1, const float* src2, int c2, float s2, const float* t, const float* aux,
-                                     const float* xt, const float* alpha, const float* beta, float* out, float* logvar,
-                                     int B, void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* src0, int c0, float s0, const float* s0_per_sample,
+                                            const float* src1, int c1, float s1, const float* src2, int c2, float s2, const float* t,
+                                            const float* aux, const float* xt, const float* alpha, const float* beta, float* out,
+                                            float* logvar, int B, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!model_ok(m)) return SWIFTK_ESHAPE;
     if (!src0 || !t || !out || !workspace || B <= 0) return SWIFTK_EINVAL;
     if (c0 + c1 + c2 != m->in_ch) return SWIFTK_ESHAPE;
@@ -210,7 +210,8 @@ extern "C" int swiftk_swinv2_forward(const swiftk_model* m, const float* src0, i
     }
 
     // patch embedding (+bias +pos_embed) into the fp32 residual stream, plus its GEMM-operand copy
-    RUN(swiftk_patchify(src0, c0, s0, src1, c1, s1, src2, c2, s2, ape, m->kpe, B, m->H, m->W, m->p1, m->p2, dt, stream));
+    RUN(swiftk_patchify_scaled(src0, c0, s0, s0_per_sample, src1, c1, s1, src2, c2, s2, ape, m->kpe, B, m->H, m->W, m->p1, m->p2, dt,
+                               stream));
     // bf16 engine: the residual stream is the pair (xT = hi, xlo = lo) from the patch embedding on; the fp32 x is never formed when
     // the embedding's epilogue can write the pair itself (8-bit low parts, whole 16-column groups), else x is split once here
     const bool pair = dt == SWIFTK_BF16 && g_fwd_pair && ntok % 16 == 0 && d % 8 == 0 && d <= 2048;
@@ -413,4 +414,12 @@ extern "C" int swiftk_swinv2_forward(const swiftk_model* m, const float* src0, i
     RUN(G(xT, m->kd, m->head_w, tok, po4, po4, kdv, d, SWIFTK_F32, SWIFTK_EPI_NONE, nullptr, nullptr, 0, (x3_exact & 32) != 0));
     RUN(swiftk_unpatchify_affine(tok, po4, xt, alpha, beta, out, B, m->out_ch, m->H, m->W, m->p1, m->p2, stream));
     return 0;
+}
+
+extern "C" int swiftk_swinv2_forward(const swiftk_model* m, const float* src0, int c0, float s0, const float* src1, int c1,
+                                     float s1, const float* src2, int c2, float s2, const float* t, const float* aux,
+                                     const float* xt, const float* alpha, const float* beta, float* out, float* logvar,
+                                     int B, void* workspace, int64_t workspace_bytes, void* stream) {
+    return swiftk_swinv2_forward_scaled(m, src0, c0, s0, nullptr, src1, c1, s1, src2, c2, s2, t, aux, xt, alpha, beta, out, logvar,
+                                        B, workspace, workspace_bytes, stream);
 }

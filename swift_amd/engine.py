@@ -23,6 +23,21 @@ from . import ops
 from ._lib import BF16X3, Layer, Model, SwiftkError, check, lib
 
 
+HEAD_DIMS = (80, 88, 96)  # window-attention widths of the bf16, exact-fp32 and split engines
+HEAD_DIMS_F32 = HEAD_DIMS + (64,)  # the exact-fp32 attention also runs 64
+
+
+def check_head_dim(module, dtype) -> None:
+    """Refuse a head width the attention kernels do not run, before anything is launched (a forward would otherwise stop
+    with a bare SWIFTK_ESHAPE from deep inside its launch sequence)."""
+    d, heads = int(module.dim), int(module.heads)
+    widths = HEAD_DIMS if dtype == torch.bfloat16 else HEAD_DIMS_F32
+    if heads <= 0 or d % heads or d // heads not in widths:
+        raise SwiftkError(f"head_dim = dim / heads = {d} / {heads} = {d / max(heads, 1):g} is not supported by the gfx950 kernels: "
+                          f"head_dim must be one of {', '.join(map(str, HEAD_DIMS))} (or 64 on the exact-fp32 attention); "
+                          f"choose model.heads so that dim / heads is one of them")
+
+
 class SwinEngine:
     def __init__(self, module, dtype):
         """``dtype``: torch.bfloat16 (bf16 MFMA engine), torch.float32 (exact-fp32 MFMA engine) or the string "bf16x3" --
@@ -40,10 +55,14 @@ class SwinEngine:
     def _param_stamp(self):
         return tuple((p.data_ptr(), p._version) for p in self.module.parameters())
 
+    def check_shape(self) -> None:
+        check_head_dim(self.module, self.dtype)
+
     def refresh(self) -> None:
         stamp = self._param_stamp()
         if stamp == self._stamp:
             return
+        self.check_shape()
         m = self.module
         dev = m.pos_embed.device
         if dev.type != "cuda":
@@ -166,8 +185,9 @@ class SwinEngine:
 
     def forward(self, srcs: Sequence[torch.Tensor], scales: Sequence[float], t: torch.Tensor,
                 aux: Optional[torch.Tensor], xt: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None,
-                beta: Optional[torch.Tensor] = None, want_logvar: bool = False):
-        """out = alpha*xt + beta*SwinV2(cat_k srcs[k]*scales[k], t, aux)   (all fp32 NCHW on the device)."""
+                beta: Optional[torch.Tensor] = None, want_logvar: bool = False, src0_scale: Optional[torch.Tensor] = None):
+        """out = alpha*xt + beta*SwinV2(cat_k srcs[k]*scales[k], t, aux)   (all fp32 NCHW on the device).  ``src0_scale``
+        ([B] fp32 on the device) multiplies source 0 per sample as well (EDM's c_in: ``swiftk_swinv2_forward_scaled``)."""
         self.refresh()
         m = self.module
         B = srcs[0].shape[0]
@@ -181,12 +201,17 @@ class SwinEngine:
         out = torch.empty(B, m.out_channels, *m.image_size, dtype=torch.float32, device=t.device)
         logvar = torch.empty(B, dtype=torch.float32, device=t.device) if want_logvar else None
         ps = [(s.data_ptr(), s.shape[1], float(c)) for s, c in zip(srcs, scales)] + [(None, 0, 1.0)] * (3 - len(srcs))
-        keep = (srcs, t, aux, xt, alpha, beta)  # noqa: F841  (alive until the launch sequence is enqueued)
-        rc = lib().swiftk_swinv2_forward(
-            C.byref(self.model), ps[0][0], ps[0][1], ps[0][2], ps[1][0], ps[1][1], ps[1][2], ps[2][0], ps[2][1], ps[2][2],
+        if src0_scale is not None:
+            src0_scale = src0_scale.reshape(-1).contiguous().float()
+            if src0_scale.numel() != B or src0_scale.device != t.device:
+                raise SwiftkError(f"src0_scale must be a [{B}] tensor on {t.device}, got {tuple(src0_scale.shape)} on {src0_scale.device}")
+        keep = (srcs, t, aux, xt, alpha, beta, src0_scale)  # noqa: F841  (alive until the launch sequence is enqueued)
+        sv = None if src0_scale is None else src0_scale.data_ptr()
+        rc = lib().swiftk_swinv2_forward_scaled(
+            C.byref(self.model), ps[0][0], ps[0][1], ps[0][2], sv, ps[1][0], ps[1][1], ps[1][2], ps[2][0], ps[2][1], ps[2][2],
             t.data_ptr(), None if aux is None else aux.data_ptr(), None if xt is None else xt.data_ptr(),
             None if alpha is None else alpha.data_ptr(), None if beta is None else beta.data_ptr(), out.data_ptr(),
             None if logvar is None else logvar.data_ptr(), B, ws.data_ptr(), ws.numel(),
             torch.cuda.current_stream().cuda_stream)
-        check(rc, "swiftk_swinv2_forward")
+        check(rc, "swiftk_swinv2_forward_scaled")
         return (out, logvar) if want_logvar else out

@@ -14,7 +14,8 @@ which caps 12 members at 6x on 8 GPUs) -- an IC's members sit next to each other
 reads each IC's state and forcing files once; rank 0 loads the checkpoint and broadcasts the
 weights over RCCL; each rank rolls its units on the device (``RolloutEngine``) and writes its
 own slices of the shared store (npy memmap, or one zarr chunk file per unit and variable:
-``utils/zarrlite.py``); a barrier closes the job.  Additive flags: ``--solver``, ``--num-steps``,
+``utils/zarrlite.py``); a barrier closes the job.  Additive flags: ``--solver`` (``edm`` is the default of an EDMPrecond
+run), ``--num-steps``,
 ``--dtype``, ``--synthetic`` (random-init weights + synthetic fields when no run directory
 exists), ``--metrics`` (ensemble RMSE / CRPS / spread-skill against the dataset's own fields,
 reduced per rank on the device and all-gathered: eval/metrics.py:39-134 without the round trip
@@ -49,8 +50,10 @@ parser.add_argument("--dump", type=str, default=None, choices=["zarr", "numpy", 
                          "rank streams 3.4 GB/s of fp32 fields (330 sample-steps/s x 9 MB + host page faults ~3 GB/s per process), "
                          "eight of them 27 GB/s into ONE filesystem.  Ask for zarr / numpy explicitly to get the raw store at any rank count)")
 # additive
-parser.add_argument("--solver", type=str, default="scm", choices=["scm", "2s", "dpm"])
-parser.add_argument("--num-steps", type=int, default=1, help="solver steps per forecast step")
+parser.add_argument("--solver", type=str, default=None, choices=["scm", "2s", "dpm", "edm"],
+                    help="default: edm for an EDMPrecond run (settings from its saved solver config), else scm")
+parser.add_argument("--num-steps", type=int, default=None, help="solver steps per forecast step (default: 1; an EDM run's "
+                    "saved solver.num_steps)")
 parser.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16", "bf16x3"],
                     help="compute engine: f32 = exact fp32 MFMA (the reference's arithmetic, factory.py:11); bf16x3 = fp32-grade "
                          "(<= 1e-4 of the reference) from split-bf16 MFMA products, about twice as fast; bf16 = throughput engine")
@@ -74,6 +77,26 @@ def synthetic_cfg() -> Cfg:
     from .config import compose
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
     return compose(here, "train", ["data=era5-synthetic-1.4"])
+
+
+def solver_setup(cfg, solver=None, num_steps=None, interval: int = 6):
+    """(solver mode, solver kwargs) of a run: a PassPrecond (TrigFlow) run defaults to 1-step "scm" at sigma 0.02..200, an
+    EDMPrecond run to "edm" with its saved ``solver`` config (reference keys: num_steps, sigma_min, sigma_max, rho, S_churn,
+    S_min, S_max, S_noise); ``num_steps`` overrides only when given, the auxiliary input is the lead time of ``interval``.
+    A solver of the other parametrisation is refused here, before any GPU work."""
+    edm = str((cfg.get("precond") or {}).get("_target_", "")).rsplit(".", 1)[-1] == "EDMPrecond"
+    solver = solver or ("edm" if edm else "scm")
+    if edm != (solver == "edm"):
+        raise ValueError(f"--solver {solver} does not match this run's precond ({'EDMPrecond' if edm else 'PassPrecond'}): "
+                         f"{'an EDM net samples with --solver edm' if edm else '--solver edm needs an EDMPrecond run'}")
+    if solver == "edm":
+        kw = {k: v for k, v in dict(cfg.get("solver") or {}).items() if k != "auxiliary"}
+        if num_steps is not None:
+            kw["num_steps"] = int(num_steps)
+    else:
+        kw = dict(num_steps=1 if num_steps is None else int(num_steps), sigma_min=0.02, sigma_max=200.0)
+    kw["auxiliary"] = interval / 10.0
+    return solver, kw
 
 
 def select_indices(n_dataset: int, samples: int, steps: int, interval: int):
@@ -329,6 +352,7 @@ def main(args):
         cfg = synthetic_cfg()
     else:
         cfg = load_saved(os.path.join(args.input, ".hydra", "config.yaml"))
+    solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
     dist.setup_torch(backend=cfg.system.torch.backend)
     np.random.seed(cfg.seed % (1 << 31))
     torch.manual_seed(np.random.randint(1 << 31))
@@ -389,8 +413,7 @@ def main(args):
         ofile = os.path.join(odir, f"{filename}.zarr")
         dist.run_on_rank0(create_empty_zarr, ofile, dataset, indices, args.members, args.steps, args.interval)
 
-    solver_kwargs = dict(num_steps=args.num_steps, sigma_min=0.02, sigma_max=200.0, auxiliary=args.interval / 10.0)
-    engine = RolloutEngine(net, dataset, interval=args.interval, solver=args.solver,
+    engine = RolloutEngine(net, dataset, interval=args.interval, solver=solver,
                            denoise_dtype={"bf16": torch.bfloat16, "f32": torch.float32, "bf16x3": "bf16x3"}[args.dtype],
                            **solver_kwargs)
     dist.log0("Rolling out samples...")

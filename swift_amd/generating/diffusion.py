@@ -8,8 +8,9 @@ Same solver names, keyword arguments and time grids as the reference's ``Diffusi
   * the remaining state arithmetic (re-noising, Heun average) runs in ``swiftk_axpby``;
   * the time grid is built on the host in fp32 with the same torch ops as the reference and
     read back once (no per-step device->host sync).
-``dpm_solver`` (:289-353, the in-training validation solver) is built the same way.  EDM-family solvers (edm_sampler,
-ablation_sampler, scm_solve2) are out of scope.
+``dpm_solver`` (:289-353, the in-training validation solver) is built the same way, and so is ``edm_sampler`` (:10-92,
+the stochastic Heun sampler of EDM nets): c_in in the gather, every Euler / Heun update in the epilogue.  ablation_sampler
+and scm_solve2 are out of scope.
 """
 from __future__ import annotations
 
@@ -61,6 +62,15 @@ def scm_time_steps(num_steps, sigma_min, sigma_max, sigma_data, intermediates=No
     elif intermediates:
         t = torch.cat([t[:1], torch.as_tensor(intermediates, dtype=torch.float32), t[-1:]])
     return t
+
+
+def edm_time_steps(num_steps: int, sigma_min: float, sigma_max: float, rho: float, dtype: torch.dtype = torch.float32
+                   ) -> torch.Tensor:
+    """diffusion.py:37-48: the rho grid with t_N = 0 appended, in ``dtype`` arithmetic (host tensor; bf16 under the bf16
+    engine, as the reference's ``torch.arange(num_steps, dtype=denoise_dtype)``)."""
+    step_indices = torch.arange(num_steps, dtype=dtype)
+    t = (sigma_max ** (1 / rho) + step_indices / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
+    return torch.cat([t, torch.zeros_like(t[:1])])
 
 
 class DiffusionSampler:
@@ -153,3 +163,54 @@ class DiffusionSampler:
                 nxt = ops.axpby(1.0, nxt, 1.0 if use_pp else -1.0, corr)
             t_prev, pred_prev, x_t = s, pred, nxt
         return x_t
+
+    @torch.no_grad()
+    def edm_sampler(self, latents: torch.Tensor, condition=None, auxiliary=None, randn_like: Callable = torch.randn_like,
+                    num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80, rho: float = 7, S_churn: float = 0,
+                    S_min: float = 0, S_max: float = float("inf"), S_noise: float = 1, pipeline_engine: bool = False,
+                    denoise_dtype=torch.bfloat16) -> torch.Tensor:
+        """EDM stochastic Heun sampler (diffusion.py:10-92, Algorithm 2 of the EDM paper): 2*num_steps-1 network calls.
+
+        The grid, gamma and t_hat are computed as the reference computes them, in ``denoise_dtype`` arithmetic (bf16 under
+        the bf16 engine, fp32 for torch.float32 and "bf16x3"), on the host.  The state stays fp32 throughout (the reference
+        keeps it in ``denoise_dtype``, i.e. bf16 under the bf16 engine).  Each step maps onto the fused call
+        alpha * xt + beta * F(c_in(sigma) x, ln(sigma) / 4) with host scalars, with h = t_next - t_hat and
+        c_skip / c_out of the noise level the network sees:
+          churn   x_hat = x + sqrt(t_hat^2 - t^2) S_noise eps               (one ``randn_like`` per step, even at gamma = 0)
+          Euler   x' = (1 + h (1 - c_skip) / t_hat) x_hat - (h c_out / t_hat) F(x_hat)      (= D at the last step, t_next = 0)
+          Heun    x  = [0.5 x_hat + (0.5 + 0.5 h (1 - c_skip') / t_next) x'] - (0.5 h c_out' / t_next) F(x')
+        with 1 - c_skip = sigma^2 / (sigma^2 + sd^2) formed directly.  No device-to-host read inside the loop."""
+        if pipeline_engine:
+            raise NotImplementedError("edm_sampler(pipeline_engine=True) is a placeholder in the reference as well")
+        mod = self._module()
+        sigma_min = max(sigma_min, mod.sigma_min)
+        sigma_max = min(sigma_max, mod.sigma_max)
+        gdt = torch.bfloat16 if denoise_dtype == torch.bfloat16 else torch.float32
+        ts = edm_time_steps(num_steps, sigma_min, sigma_max, rho, gdt)
+        sd = float(mod.sigma_data)
+        dev = latents.device
+        x = (latents.float() * float(ts[0])).contiguous()
+
+        def call(x_in, sigma, xt, alpha, beta):
+            with engine_for(mod, denoise_dtype, dev.type):
+                return self.net(x_in, sigma, condition, auxiliary, xt=xt, alpha=alpha, beta=beta)
+
+        for i in range(num_steps):
+            t_cur, t_next = ts[i], ts[i + 1]
+            gamma = min(S_churn / num_steps, math.sqrt(2) - 1) if bool(S_min <= t_cur <= S_max) else 0
+            t_hat = t_cur + gamma * t_cur
+            eps = randn_like(x)  # (drawn at gamma = 0 too: the noise streams stay aligned with the reference's)
+            c = float((t_hat ** 2 - t_cur ** 2).sqrt()) * S_noise
+            x_hat = ops.axpby(1.0, x, c, eps.contiguous().float()) if c != 0.0 else x
+            th, tn, h = float(t_hat), float(t_next), float(t_next - t_hat)
+            s2 = th * th + sd * sd
+            a = 1.0 + h * (th * th / s2) / th
+            b = -h * (th * sd / math.sqrt(s2)) / th
+            x_e = call(x_hat, th, x_hat, a, b)  # Euler step
+            if i < num_steps - 1:
+                s2n = tn * tn + sd * sd
+                half = ops.axpby(0.5, x_hat, 0.5 + 0.5 * h * (tn * tn / s2n) / tn, x_e)
+                x = call(x_e, tn, half, 1.0, -0.5 * h * (tn * sd / math.sqrt(s2n)) / tn)  # 2nd-order correction
+            else:
+                x = x_e
+        return x

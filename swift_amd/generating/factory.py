@@ -1,7 +1,8 @@
 """Sampler closures (mirrors reference src/swift/generating/factory.py:8-97).
 
 ``sampler_factory(mode, net, denoise_dtype, **solver_kwargs) -> sampler(X, generator)`` with
-modes "scm" and "2s".  Latents are drawn exactly like the reference (``torch.randn`` with the
+modes "scm", "2s", "dpm" (TrigFlow nets, ``PassPrecond``) and "edm" (``EDMPrecond`` nets).  A mode of the other
+parametrisation is refused: the reference would run it and silently mix the two.  Latents are drawn exactly like the reference (``torch.randn`` with the
 caller's generator on X's device, factory.py:52-56) -- RNG is torch plumbing, not part of the
 hand-written path; parity tests inject latents through ``latents=``.
 """
@@ -18,6 +19,12 @@ def sampler_factory(mode: str, net: torch.nn.Module, denoise_dtype: torch.dtype 
                     **solver_kwargs) -> Callable[..., torch.Tensor]:
     O = DiffusionSampler(net)
     mod = getattr(net, "module", net)
+    from ..models.precond import EDMPrecond, PassPrecond
+    if mode == "edm" and isinstance(mod, PassPrecond):
+        raise ValueError("solver 'edm' needs an EDMPrecond net (EDM parametrisation); this net is a PassPrecond (TrigFlow): "
+                         "use 'scm', '2s' or 'dpm'")
+    if mode in ("scm", "2s", "dpm") and isinstance(mod, EDMPrecond):
+        raise ValueError(f"solver {mode!r} assumes a TrigFlow net (PassPrecond); this net is an EDMPrecond: use 'edm'")
     if mode == "scm":
         solve = O.scm_solver
     elif mode == "2s":
@@ -25,7 +32,7 @@ def sampler_factory(mode: str, net: torch.nn.Module, denoise_dtype: torch.dtype 
     elif mode == "dpm":
         solve = O.dpm_solver
     elif mode == "edm":
-        raise NotImplementedError(f"solver mode {mode!r} is outside the sCM/TrigFlow forecast path built here")
+        solve = O.edm_sampler
     else:
         raise ValueError(f"Unknown solver mode: {mode}")
 

@@ -175,8 +175,9 @@ class SwinV2(AbstractNetwork):
 
     def forward_sources(self, srcs: Sequence[torch.Tensor], scales: Sequence[float], t: torch.Tensor,
                         auxiliary: Optional[torch.Tensor] = None, return_logvar: bool = False, xt=None, alpha=None,
-                        beta=None, dtype: Optional[torch.dtype] = None):
-        """Network on the channel-concatenation of ``srcs`` without materialising the concat."""
+                        beta=None, dtype: Optional[torch.dtype] = None, src0_scale: Optional[torch.Tensor] = None):
+        """Network on the channel-concatenation of ``srcs`` without materialising the concat (``src0_scale``: an extra
+        per-sample [B] factor on ``srcs[0]``, applied in the patch gather)."""
         B = srcs[0].shape[0]
         t = self._prep_t(t, B)
         aux = None
@@ -185,7 +186,8 @@ class SwinV2(AbstractNetwork):
             if aux.shape[0] == 1 and B > 1:  # precond.py:25 hands a [1, aux_dim] zero row when auxiliary is None
                 aux = aux.expand(B, -1)
         want_lv = bool(self.logvar_embed is not None and return_logvar)
-        return self.engine(dtype).forward(srcs, scales, t, aux, xt=xt, alpha=alpha, beta=beta, want_logvar=want_lv)
+        return self.engine(dtype).forward(srcs, scales, t, aux, xt=xt, alpha=alpha, beta=beta, want_logvar=want_lv,
+                                          src0_scale=src0_scale)
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, auxiliary: Optional[torch.Tensor] = None, jvp: bool = False,
                 return_logvar: bool = False):

@@ -89,7 +89,9 @@ class RolloutEngine:
         if "randn_like" not in kw:
             kw["randn_like"] = self._randn_like
         self.sampler = sampler_factory(solver, net, denoise_dtype=denoise_dtype, **kw)
-        self.renoises = solver == "scm" and int(kw["num_steps"]) > 1  # (diffusion.py:452-455: draws between network calls)
+        # (diffusion.py:452-455: draws between network calls; EDM's churn, diffusion.py:58-63, draws once per Heun step)
+        self.renoises = ((solver == "scm" and int(kw["num_steps"]) > 1)
+                         or (solver == "edm" and float(kw.get("S_churn", 0)) > 0))
         self.residual = getattr(dataset, "residual", False)  # generate.py:76
         self._stats = None
 

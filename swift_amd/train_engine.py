@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from ._lib import (ATTN_PRENORM, BF16, EPI_ACCUM, EPI_BIAS_POS, EPI_NONE, EPI_QKNORM, EPI_SWIGLU_BOTH, EPI_SWIGLU_BWD, F32, SwiftkError, check, lib)
+from .engine import check_head_dim
 from .graphs import GraphCache
 
 _BF = torch.bfloat16
@@ -71,6 +72,7 @@ def _padded(rows, width, valid):
 class SwinTrainEngine:
     def __init__(self, module):
         self.m = module
+        check_head_dim(module, torch.bfloat16)  # (names head_dim and the widths the kernels run)
         self.hd = module.dim // module.heads
         if self.hd not in (80, 88, 96) or module.heads % 2:
             raise SwiftkError("the training kernels are built for head_dim 80 / 88 / 96 and an even head count")

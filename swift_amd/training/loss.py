@@ -1,6 +1,7 @@
-"""TrigFlow and multistep-CRPS losses on the gfx950 training kernels (mirrors reference src/swift/training/loss.py).
+"""TrigFlow, EDM and multistep-CRPS losses on the gfx950 training kernels (mirrors reference src/swift/training/loss.py).
 
-Same constructor kwargs and call signatures as the reference's ``TrigFlowLoss`` (:117-160) and ``CRPSLoss`` (:306-445):
+Same constructor kwargs and call signatures as the reference's ``TrigFlowLoss`` (:117-160), ``EDMLoss`` (:95-114) and
+``CRPSLoss`` (:306-445):
 ``loss = loss_fn(net_or_ddp, target, condition=x, auxiliary=delta, **kw)``; ``loss.backward()`` accumulates parameter
 gradients.  The backward pass is not an autograd graph: the returned scalar hangs on a one-node ``autograd.Function``
 whose backward runs the explicit kernels of ``train_engine`` (for the multistep loss: one rollout step at a time,
@@ -72,6 +73,12 @@ class _Deferred(torch.autograd.Function):
     def backward(ctx, g):
         ctx.runner.run_backward(g.detach().float())  # stays a device scalar: reading it would stall the host behind the GPU
         return None, None
+
+
+def _refuse_edm(net, what: str) -> None:
+    from ..models.precond import EDMPrecond
+    if isinstance(getattr(net, "module", net), EDMPrecond):
+        raise ValueError(f"{what} assumes a TrigFlow-parametrised net (PassPrecond); this net is an EDMPrecond: train it with EDMLoss")
 
 
 def _engine(net) -> SwinTrainEngine:
@@ -179,6 +186,60 @@ class TrigFlowLoss(_LossBase):
         return _Deferred.apply(self._anchor(dev), Runner)
 
 
+class EDMLoss(_LossBase):
+    """loss = mean_{b,h,w} sum_c lambda(sigma) w_var w_lat (D(x + sigma z; sigma) - x)^2,  lambda = (sigma^2 + sd^2) / (sigma sd)^2
+    (loss.py:95-114).
+
+    Same constructor and call signature as the reference; sigma ([B,1,1,1], from ``noise``) is drawn before z, as there.
+    ``swiftk_edm_prep`` writes the network input c_in (x + sigma z), which the training engine takes as source 0 at scale 1;
+    ``swiftk_edm_loss`` forms D - x from F in one pass (in a form that keeps fp32 accuracy at small sigma) and writes
+    dF for the deferred backward.  ``_sigma`` / ``_z`` inject the draws (parity tests)."""
+
+    def __init__(self, dataset, noise: dict, sigma_data: float):
+        super().__init__(dataset, sigma_data)
+        self.cfg = dict(noise)
+        self._sampling_fn = partial(NOISE_SAMPLING_METHODS[self.cfg.pop("dist")], **self.cfg)
+
+    def forward(self, net, x, condition=None, auxiliary=None, *, _sigma=None, _z=None):
+        mod = getattr(net, "module", net)
+        from ..models.precond import EDMPrecond
+        if not isinstance(mod, EDMPrecond):
+            raise ValueError(f"EDMLoss trains an EDMPrecond net; got {type(mod).__name__}")
+        eng = _engine(net)
+        dev = x.device
+        B, C, H, W = x.shape
+        sd = float(self.sigma_data)
+        sigma = (self._sampling_fn(x) if _sigma is None else _sigma).reshape(B).to(dev, torch.float32).contiguous()
+        z = (torch.randn_like(x) if _z is None else _z).contiguous().float()
+        x = x.contiguous().float()
+        net_in = torch.empty_like(x)
+        st = torch.cuda.current_stream().cuda_stream
+        check(lib().swiftk_edm_prep(x.data_ptr(), z.data_ptr(), sigma.data_ptr(), net_in.data_ptr(), sd, B, C * H * W, st),
+              "swiftk_edm_prep")
+        t = (torch.log(sigma) / 4).contiguous()  # c_noise ([B] coefficient math)
+        aux = _process_auxiliary(auxiliary, mod.auxiliary_dim, B, dev)
+        srcs, scales = [net_in], [1.0]
+        if condition is not None and mod.condition_channels > 0:
+            srcs.append(condition)
+            scales.append(1.0)
+        Fx, ctx = eng.forward(srcs, scales, t, aux, want_logvar=False)
+        wv, wl = self._w(dev)
+        loss = ops.zeros_acc(1, device=dev)
+        dF = torch.empty_like(Fx)
+        check(lib().swiftk_edm_loss(Fx.data_ptr(), x.data_ptr(), z.data_ptr(), sigma.data_ptr(), wv.data_ptr(), wl.data_ptr(),
+                                    loss.data_ptr(), dF.data_ptr(), sd, B, C, H, W, 1.0, st), "swiftk_edm_loss")
+
+        class Runner:
+            value = loss.reshape(())
+
+            @staticmethod
+            def run_backward(g):
+                dF.mul_(g)
+                eng.backward(ctx, dF, None, grads_final=getattr(net, "reduce_params", None))
+
+        return _Deferred.apply(self._anchor(dev), Runner)
+
+
 class SCMLoss(_LossBase):
     """Continuous-time consistency (sCM) loss, loss.py:163-260, with the tangent from ``jvp_engine.SwinJvpEngine``.
 
@@ -206,6 +267,7 @@ class SCMLoss(_LossBase):
         return eng
 
     def forward(self, net, x, step, condition=None, auxiliary=None, net_pretrained=None, _tau=None, _z=None, **kwargs):
+        _refuse_edm(net, "SCMLoss")
         mod = getattr(net, "module", net)
         eng = _engine(net)
         dev = x.device
@@ -330,6 +392,7 @@ class CRPSLoss(_LossBase):
         return out
 
     def forward(self, net, target, condition, auxiliary, idx, steps: int = 1, chunk_size: int = 2, _latents=None, **kwargs):
+        _refuse_edm(net, "CRPSLoss")
         mod = getattr(net, "module", net)
         eng = _engine(net)
         dev = target.device

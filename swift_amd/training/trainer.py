@@ -22,7 +22,7 @@ import torch
 import torch.distributed as tdist
 
 from .. import dist, ops
-from .loss import CRPSLoss, SCMLoss, TrigFlowLoss
+from .loss import CRPSLoss, EDMLoss, SCMLoss, TrigFlowLoss
 
 
 class GradAllReduce(torch.nn.Module):
@@ -242,7 +242,10 @@ class Trainer:
             self.resume_kimg = 0
         self.loss_fn, self.optimizer = loss_fn, optimizer
         self.val_ticks, self.val_target_interval, self.val_variables = val_ticks, val_target_interval, val_variables
-        self.solver_type, self.solver_kwargs = "dpm", dict(solver_kwargs or {})  # trainer.py:136-137
+        self.solver_type = "edm" if isinstance(loss_fn, EDMLoss) else "dpm"  # trainer.py:136-137
+        self.solver_kwargs = dict(solver_kwargs or {})
+        if val_ticks:
+            dist.log0(f"in-training validation: solver {self.solver_type} {self.solver_kwargs}")
         self.net_pretrained = None if net_pretrained is None else net_pretrained.to(self.device).eval()  # trainer.py:119-123
         self.lr_rampup_kimg, self.lr_min_factor, self.lr_cosine_anneal = lr_rampup_kimg, lr_min_factor, lr_cosine_anneal
         self.finetune_kwargs = dict(finetune_kwargs or {})

@@ -63,10 +63,11 @@ def install_stubs():
 install_stubs()
 from swift.data.era5 import ERA5Dataset  # noqa: E402
 from swift.generating.factory import sampler_factory  # noqa: E402
-from swift.models.precond import PassPrecond  # noqa: E402
+from swift.models.precond import EDMPrecond, PassPrecond  # noqa: E402
 from swift.models.swinv2 import SwinV2, timestep_embedding  # noqa: E402
 from swift.training.loss import (  # noqa: E402
     CRPSLoss,
+    EDMLoss,
     SCMLoss,
     TrigFlowLoss,
     _calculate_latitude_weights,
@@ -681,7 +682,78 @@ def fx_swiftb_fp64():
          y1_norm=float(y1.norm()), y2s_norm=float(y2.norm()))
 
 
-ALL = dict(swiftb_fp64=fx_swiftb_fp64, swiftb_2s_bf16=fx_swiftb_2s_bf16, scm_distill_tiny=fx_scm_distill_tiny, index_streams=fx_index_streams, era5_tiny=fx_era5_tiny, swiftb_long=fx_swiftb_long, trainer_tiny=fx_trainer_tiny, metrics_tiny=fx_metrics_tiny, val_tiny=fx_val_tiny, muon_tiny=fx_muon_tiny, swinv2_tiny=fx_swinv2_tiny, swinv2_smallb=fx_swinv2_smallb, attention_hd88=fx_attention_hd88,
+def fx_edm_tiny():
+    """EDMPrecond (precond.py:39-98), edm_sampler (diffusion.py:10-92) and EDMLoss (loss.py:95-114) at the TINY shape."""
+    c, seed = TINY, 11
+    nv, nf = c["n_vars"], c["n_forc"]
+    net = EDMPrecond(model_cfg(c), img_resolution=list(c["img"]), img_channels=nv, condition_channels=nv + nf, auxiliary_dim=1,
+                     sigma_min=0, sigma_max=float("inf"), sigma_data=0.5)
+    grid = (c["img"][0] // c["patch"][0], c["img"][1] // c["patch"][1])
+    state = swinv2_state(grid=grid, in_channels=2 * nv + nf, out_channels=nv, patch_size=c["patch"], depth=c["depth"],
+                         dim=c["dim"], heads=c["heads"], auxiliary_dim=1, seed=seed)
+    net.load_state_dict(state, strict=True)
+    net.eval()
+    out = {"state_keys": np.array(list(net.state_dict().keys()))}
+    B = 3
+    x = det_normal((B, nv, *c["img"]), seed, "x")
+    cond = det_normal((B, nv + nf, *c["img"]), seed, "cond")
+    aux = torch.tensor([0.6, 0.6, 0.6])
+    sig = torch.tensor([0.01, 0.5, 80.0])
+    with torch.no_grad():
+        out["precond"] = net(x, sig, cond, aux)
+    # edm_sampler, N = 4, churn on, injected noise, fp32
+    from swift.generating.diffusion import DiffusionSampler
+    S = DiffusionSampler(net)
+    Bs = 2
+    lat = det_normal((Bs, nv, *c["img"]), seed, "lat")
+    ren = [det_normal((Bs, nv, *c["img"]), seed, f"ren{i}") for i in range(4)]
+    it = iter(ren)
+    skw = dict(num_steps=4, sigma_min=0.03, sigma_max=80.0, rho=7, S_churn=2.5, S_min=0.75, S_max=80, S_noise=1.05, auxiliary=0.6)
+    with torch.no_grad():
+        out["sampler"] = S.edm_sampler(lat.clone(), condition=cond[:Bs], randn_like=lambda like: next(it).to(like),
+                                       denoise_dtype=torch.float32, **skw)
+
+    class Recorder:  # the sigmas edm_sampler hands the net = its t_steps (S_churn = 0: t_hat = t_cur)
+        sigma_min, sigma_max = 0, float("inf")
+
+        def __init__(self):
+            self.seen = []
+
+        def round_sigma(self, s):
+            return torch.as_tensor(s)
+
+        def __call__(self, x, sigma, *a, **k):
+            self.seen.append(sigma.reshape(()).clone())
+            return x
+
+    gkw = dict(num_steps=20, sigma_min=0.03, sigma_max=80.0, rho=7)  # configs/solver/edm.yaml
+    for name, dt in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+        rec = Recorder()
+        DiffusionSampler(rec).edm_sampler(torch.zeros(1, 1, 2, 2), denoise_dtype=dt, **gkw)
+        ts = [rec.seen[0]] + rec.seen[1::2]  # t_0, then every step's t_next (the Heun call)
+        out[f"t_steps_{name}"] = torch.stack(ts).float()
+    # EDMLoss with the reference's draw order: sigma ~ lognormal [B,1,1,1], then z = randn_like(x)
+    bank = det_normal((B + 8, nf, *c["img"]), seed, "forc")
+    ds = FakeERA5(c, seed, bank)
+    ds.variables = ["2m_temperature", "10m_u_component_of_wind", "geopotential_500", "temperature_850"]
+    net.train().requires_grad_(True)
+    noise = dict(dist="lognormal", P_mean=-0.2, P_std=2.2)
+    L = EDMLoss(ds, dict(noise), sigma_data=0.5)
+    torch.manual_seed(41)
+    val = L(FakeDDP(net), x, condition=cond, auxiliary=aux)
+    val.backward()
+    gsel = ["model.head.head.0.weight", "model.transformer.layers.1.0.to_qkv.weight", "model.pos_embed",
+            "model.transformer.layers.0.1.norm.modulation.weight", "model.transformer.layers.2.0.scale"]
+    named = dict(net.named_parameters())
+    out["loss"], out["loss_g"] = float(val), np.array([float(named[k].grad.norm()) for k in gsel])
+    torch.manual_seed(41)
+    out["loss_sigma"] = torch.exp(torch.randn([B, 1, 1, 1]) * noise["P_std"] + noise["P_mean"])
+    out["loss_z"] = torch.randn_like(x)
+    save("edm_tiny", seed=seed, fingerprint=state_fingerprint(state), x=x, cond=cond, aux=aux, sigma=sig, lat=lat,
+         **{f"ren{i}": r for i, r in enumerate(ren)}, grad_keys=np.array(gsel), w_lat=L.w_lat, w_var=L.w_var, **out)
+
+
+ALL = dict(edm_tiny=fx_edm_tiny, swiftb_fp64=fx_swiftb_fp64, swiftb_2s_bf16=fx_swiftb_2s_bf16, scm_distill_tiny=fx_scm_distill_tiny, index_streams=fx_index_streams, era5_tiny=fx_era5_tiny, swiftb_long=fx_swiftb_long, trainer_tiny=fx_trainer_tiny, metrics_tiny=fx_metrics_tiny, val_tiny=fx_val_tiny, muon_tiny=fx_muon_tiny, swinv2_tiny=fx_swinv2_tiny, swinv2_smallb=fx_swinv2_smallb, attention_hd88=fx_attention_hd88,
            samplers_tiny=fx_samplers_tiny, rollout_tiny=fx_rollout_tiny, losses_tiny=fx_losses_tiny,
            swiftb_step=fx_swiftb_step, weights_aux=fx_weights_aux)
 
