@@ -139,7 +139,11 @@ __global__ __launch_bounds__(256) void modnorm_jvp_scalar_kernel(const T* __rest
         s1 += dv[i];
     }
     const float inv_d = 1.0f / (float)d;
-    const float mu = wave_sum(s0) * inv_d, mdy = wave_sum(s1) * inv_d;
+    // The two means by a true division, not `sum * inv_d`: that product gets contracted into the subtractions below
+    // (y - sum * inv_d as one fma), which then see the UNROUNDED product and with it the rounding error of inv_d -- 40 * 6e-8 on a
+    // row that sits at 40, times rstd = 1e3 when the row is constant: n = 2e-3 where it is 0 (tests/test_gpu_tangent_kernels.py,
+    // hostile row 1: x off by 6.4e-4 of the row's maximum before, 4e-8 after).  A quotient cannot be fused, and is exact for such a row.
+    const float mu = wave_sum(s0) / (float)d, mdy = wave_sum(s1) / (float)d;
     float s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 24; ++i) {

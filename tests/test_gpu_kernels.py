@@ -298,6 +298,46 @@ def test_modnorm_residual_pair(dev, rps, lo_bits, d):
     assert rel_l2(got, xd.cpu()) < 1e-5
 
 
+@pytest.mark.parametrize("rps", [512, 48])
+@pytest.mark.parametrize("d", [1056, 1280, 1536])
+def test_modnorm_residual_pair_to(dev, rps, d):
+    """swiftk_modnorm_residual_pair_to, the training forward's form (the new hi goes to ANOTHER buffer, every layer's operand being
+    a saved activation), at the shapes of test_modnorm_residual_pair with the 8-bit low part: bit-equal to the in-place call on a
+    copy, the input hi unchanged, the output's pad columns untouched.  d = 1536 has no out-of-place kernel: SWIFTK_ESHAPE, nothing
+    written.  A missing output buffer is SWIFTK_EINVAL."""
+    from swift_amd import _lib, ops
+    L = _lib.lib()
+    B = 3
+    M = B * rps
+    y, x = rnd((M, d), 12, 2.0) + 0.5, rnd((M, d), 13)
+    gamma, beta = (1 + 0.1 * rnd((d,), 14)).to(dev), (0.1 * rnd((d,), 15)).to(dev)
+    mod = (0.3 * rnd((B, 5 * 2 * d), 16)).to(dev)[:, 4 * d: 6 * d]
+    ld = ops.k_pad(torch.bfloat16, d)
+    hi, lo = ops.split_pair(x.to(dev), ld, 8)
+    yd = to_dt(y, torch.bfloat16, dev)
+    hi_ref, lo_ref = hi.clone(), lo.clone()
+    ops.modnorm_residual_pair(yd, hi_ref, lo_ref, gamma, beta, mod, rps, d)
+    hi_in, lo_to = hi.clone(), lo.clone()
+    hi_out = torch.full((M, ld), 7.0, dtype=torch.bfloat16, device=dev)
+    hi_out[:, :d] = float("nan")
+    poisoned = hi_out.clone()
+    s = torch.cuda.current_stream().cuda_stream
+    args = lambda out: (yd.data_ptr(), yd.stride(0), hi_in.data_ptr(), out, ld, lo_to.data_ptr(), d, 8, gamma.data_ptr(), beta.data_ptr(),
+                        mod.data_ptr(), mod.stride(0), M, d, rps, 1e-6, s)
+    assert L.swiftk_modnorm_residual_pair_to(*args(None)) == -1   # SWIFTK_EINVAL
+    rc = L.swiftk_modnorm_residual_pair_to(*args(hi_out.data_ptr()))
+    torch.cuda.synchronize()
+    w = lambda t: t.contiguous().view(torch.int16)
+    assert torch.equal(w(hi_in), w(hi))
+    if d == 1536:
+        assert rc == -2   # SWIFTK_ESHAPE
+        assert torch.equal(w(hi_out), w(poisoned)) and torch.equal(lo_to, lo)
+        return
+    assert rc == 0
+    assert torch.equal(w(hi_out[:, :d]), w(hi_ref[:, :d])) and torch.equal(lo_to, lo_ref)
+    assert (hi_out[:, d:].float() == 7.0).all()
+
+
 def test_unit_noise_vs_oracle(dev):
     """swiftk_unit_noise: the generator's words bit for bit against the numpy Philox4x32-10 of oracle/noise.py (which
     tests/test_oracle_golden.py pins to Random123's known answers), the normals against its Box-Muller, and the properties a

@@ -202,6 +202,66 @@ def test_modnorm_bwd(dev, rps, d, fused):
     assert float(dmod[:, : 2 * d].abs().max()) == 0.0 and (dy.shape[1] == d or float(dy[:, d:].float().abs().max()) == 0.0)
 
 
+@pytest.mark.parametrize("rps,d,fused", [(96, 1056, 1), (1088, 1056, 1), (1088, 1056, 0), (1536, 1536, 1), (1280, 1280, 2), (256, 1056, 1)])
+def test_modnorm_bwd_ws0(dev, rps, d, fused):
+    """swiftk_modnorm_bwd_ws0, the form every training backward calls (train_engine.py), at the shapes of test_modnorm_bwd: the caller
+    keeps the workspace zero, the finishing kernel zeroes what it has read.  Same gradient bounds as test_modnorm_bwd; the workspace
+    is all zero on return; a second call on the un-cleared workspace doubles dgamma / dbeta / dmod (they accumulate) and repeats
+    dy; where swiftk_modnorm_bwd would take the two-kernel form the call is refused and nothing is written."""
+    from swift_amd import _lib, ops
+    L = _lib.lib()
+    B = 3
+    M = B * rps
+    y = (rnd((M, d), 5, 2.0) + 0.3).to(dev).to(BF)
+    g = rnd((M, d), 6).to(dev)
+    gamma, beta = (1 + 0.1 * rnd((d,), 7)).to(dev), (0.1 * rnd((d,), 8)).to(dev)
+    mod = (0.3 * rnd((B, 3 * 2 * d), 9)).to(dev)
+    msl = mod[:, 2 * d: 4 * d]
+    one_kernel = fused > 0 and rps >= d   # (rows_per_sample is a multiple of 64 at every shape here)
+    dy = torch.full((M, ops.k_pad(BF, d)), 0.0 if one_kernel else 7.0, dtype=BF, device=dev)
+    fill = 0.0 if one_kernel else 7.0
+    dgam, dbet = torch.full((d,), fill, device=dev), torch.full((d,), fill, device=dev)
+    dmod = torch.full((B, 3 * 2 * d), fill, device=dev)
+    dsl = dmod[:, 2 * d: 4 * d]
+    ws = torch.full((2 * B * d,), fill, device=dev)   # zeroed once, by the test
+
+    def call():
+        L.swiftk_set_tuning(16, fused)
+        try:
+            return L.swiftk_modnorm_bwd_ws0(y.data_ptr(), d, g.data_ptr(), dy.data_ptr(), dy.stride(0), gamma.data_ptr(), beta.data_ptr(),
+                                            msl.data_ptr(), msl.stride(0), dgam.data_ptr(), dbet.data_ptr(), dsl.data_ptr(), dsl.stride(0),
+                                            ws.data_ptr(), M, d, rps, 1e-6, _lib.BF16, s())
+        finally:
+            L.swiftk_set_tuning(16, 1)
+
+    rc = call()
+    torch.cuda.synchronize()
+    if not one_kernel:
+        assert rc == -2   # SWIFTK_ESHAPE
+        for t in (dy, dgam, dbet, dmod, ws):
+            assert (t.float() == 7.0).all()
+        return
+    assert rc == 0
+    assert float(ws.abs().max()) == 0.0 and not bool(ws.view(torch.int32).any())   # zero again, + 0 in every word
+    yc = y.float().cpu().requires_grad_(True)
+    gc, bc = gamma.cpu().requires_grad_(True), beta.cpu().requires_grad_(True)
+    mc = msl.cpu().clone().requires_grad_(True)
+    ln = F.layer_norm(yc.view(B, rps, d), (d,), gc, bc, 1e-6)
+    out = ln * (1 + mc[:, None, :d]) + mc[:, None, d:]
+    out.backward(g.cpu().view(B, rps, d))
+    assert rel_l2(dy[:, :d].float().cpu(), yc.grad) < 6e-3
+    assert rel_l2(dgam.cpu(), gc.grad) < 1e-4 and rel_l2(dbet.cpu(), bc.grad) < 1e-4
+    assert rel_l2(dsl.cpu(), mc.grad) < 1e-4
+    assert float(dmod[:, : 2 * d].abs().max()) == 0.0 and (dy.shape[1] == d or float(dy[:, d:].float().abs().max()) == 0.0)
+    first = [t.clone() for t in (dy, dgam, dbet, dmod)]
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert float(ws.abs().max()) == 0.0
+    assert torch.equal(dy, first[0])
+    for got, one in zip((dgam, dbet, dmod), first[1:]):
+        assert rel_l2(got.cpu(), 2 * one.cpu().double()) < 1e-5
+
+
 def _prenorm(qkv, scale, heads, hd):
     B, n, _ = qkv.shape
     v = qkv.reshape(B, n, heads, 3, hd)
