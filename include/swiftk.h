@@ -381,11 +381,13 @@ int swiftk_gemm_batched(const void* A, int64_t lda, int64_t stride_a, const void
                         int64_t ldc, int64_t stride_c, int batch, int64_t M, int64_t N, int64_t K, int dtype, int out_dtype,
                         void* stream);
 /* slabs[s][M, ldc] (fp32) = A[M, K_s] * W[N, K_s]^T for the s-th of `ksplit` equal k-ranges; slab s starts at
- * slabs + s*slab_stride.  Same operand rules as swiftk_gemm; M % 8 == 0, N % 8 == 0. */
+ * slabs + s*slab_stride.  Same operand rules as swiftk_gemm; M % 8 == 0, N % 8 == 0.  k-range s covers the k-tiles (128 B of a
+ * row) [s T / ksplit, (s + 1) T / ksplit) of the T the contraction has; ksplit > T is SWIFTK_ESHAPE (no empty ranges). */
 int swiftk_gemm_splitk(const void* A, int64_t lda, const void* W, int64_t ldw, float* slabs, int64_t ldc, int64_t slab_stride,
                        int64_t M, int64_t N, int64_t K, int dtype, int ksplit, void* stream);
 /* Split-K with bf16 slabs (bf16 operands; M, N % 8 == 0): slab s = bf16(A[:, k-range s] W[:, k-range s]^T), each partial product
- * rounded once as a plain bf16 GEMM rounds its output.  The forecast path's wo / w2 at one unit per step. */
+ * rounded once as a plain bf16 GEMM rounds its output.  The forecast path's wo / w2 at one unit per step.  The k-ranges are those of
+ * swiftk_gemm_splitk; ksplit greater than the number of k-tiles is SWIFTK_ESHAPE (no empty ranges). */
 int swiftk_gemm_splitk_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* slabs, int64_t ldc, int64_t slab_stride,
                             int64_t M, int64_t N, int64_t K, int ksplit, void* stream);
 /* y = A[M, K] W[N, K]^T (bf16, N % 352 == 0: the d-wide Linears wo / w2, swinv2.py:112-113 / :134) for batches whose tile count leaves

@@ -1827,6 +1827,9 @@ static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, voi
     if (K % tile_k != 0 || N % 4 != 0) return SWIFTK_ESHAPE;
     if (M > (1 << 30) || N > (1 << 30) || K > (1 << 30)) return SWIFTK_ESHAPE;
     if (lda < K || ldw < K) return SWIFTK_ESHAPE;
+    // every k-range holds at least one k-tile (as swiftk_gemm_tn_splitk demands): the persistent walk ends a work item on the LAST
+    // k-tile of its range, and an empty range has none -- its k-loop would run on past the operands' rows
+    if (ksplit > K / tile_k) return SWIFTK_ESHAPE;
     const int ovec = (epilogue == SWIFTK_EPI_SWIGLU || epilogue == SWIFTK_EPI_SWIGLU_SPLIT3 ? 2 : 4) * os;
     if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || (lda * es) % 16 || (ldw * es) % 16) return SWIFTK_EALIGN;
     if (((uintptr_t)C % ovec) || (ldc * os) % ovec) return SWIFTK_EALIGN;
