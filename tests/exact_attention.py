@@ -1,0 +1,443 @@
+"""Inputs with ONE right answer for the window-attention family: builders, CPU references and the case table (no GPU here).
+
+Two input families make softmax(q k^T) v independent of how a kernel rounds, orders or normalises:
+
+  selector  one-hot softmax.  Per (sample, window, head) item the 256 keys are random +-1 code vectors (largest off-diagonal |cos|
+            <= COS_CAP, a seeded retry loop) times a positive magnitude; query i is the code of key pi(i) for a random permutation pi
+            of the item.  At a logit scale tau >= 30 every wrong key sits >= tau (1 - COS_CAP) = 13.5 below the right one, the
+            wrong keys' total weight stays far below half a bf16 ulp of any v (tests/test_exact_attention_cpu.py proves it on the
+            oracle for every row), and the output is v[pi(i)]: a gather.  v is bf16-valued (+-[1, 2) 2^e, e in -1..2, drawn per
+            element), so that a misrouted, stale or dropped element shows.  The code vectors all have the norm sqrt(head_dim) and
+            entries of one magnitude, so rounding q-hat tau and k-hat to bf16 only rescales every logit of an item by one factor.
+            fp32 kernels are run at tau >= 49, where the fp32 result equals the gather bit for bit as well.
+  uniform   all 256 keys of an item are one random vector, q is random, v is ternary.  Every probability is 1/256 whatever the
+            logit, the column sum S is an integer of magnitude <= 256 (every partial sum too) and S / 256 is a bf16 value: one bit
+            pattern whether the kernel divides, multiplies by a reciprocal, subtracts a maximum or not.  Pins "every key is summed
+            exactly once" in both softmax forms, which the selector cannot see.
+
+For swiftk_qkv_attention_fused (and swiftk_gemm_qkv_tiled) q / k / v are PRODUCTS, so the structure goes into x and W
+(`fused_operands`): x has +-1 entries, block h of a token's row is base[sigma_h(i)], W_k of head h selects block h, W_q block h + 1,
+so query i of head h is the key code of pi_h(i) = sigma_h^-1(sigma_{h+1}(i)); W_v holds integers in [-2, 2] with an odd number of odd
+entries per row, so every v is an exact ODD integer (never 0: a zero would turn the wrong keys' 1e-7 weight into the whole result).
+
+Backward (selector): with P one-hot dv[pi(i)] = dO[i], a scatter, bit for bit.  dq and dk are what is left of the cancellation
+dS_i,pi = dP_i,pi - D_i, two fp32 sums of the same head_dim products dO_ic v_pi,c: |dS_i,pi| <= 2 gamma sum_c |dO_ic v_pi,c| with
+gamma = hd u / (1 - hd u) and u = 2^-23 (a unit roundoff that also covers an add inside the matrix pipe that does not round to
+nearest); dq_i = dS k-hat_pi and dk_pi = dS q-hat_i then carry one bf16 rounding of dS (the matrix operand) and one of the stored
+value (RNE is monotone: each is a factor <= 1 + 2^-9).  `selector_backward` returns these per-element bounds.  Uniform: P = 2^-8
+everywhere, dv[j] = sum_i dO[i] / 256 with ternary dO, exact again.
+
+Everything expected comes from oracle.window_token_index and gathers; nothing from the HIP library enters a reference.
+Tensors are built in WINDOW order [B, windows, heads, 256, ...] and scattered to token order through the oracle's index map.
+"""
+from __future__ import annotations
+
+import math
+import zlib
+from dataclasses import dataclass
+from functools import lru_cache
+
+import torch
+
+from oracle.swinv2 import window_token_index
+
+COS_CAP = 0.55
+SENT_F32 = 0x7FC12345          # quiet NaNs with a payload nothing computes
+SENT_BF16 = 0x7FC1
+ESHAPE = -2
+U_PIPE = 2.0 ** -23            # unit roundoff assumed for an fp32 add inside the matrix pipe (not necessarily RNE)
+TAUS = (30.0, 40.0, 49.0, 150.0, 47.0, 60.0, 48.0, 100.0, 30.0, 49.5, 75.0, 44.0)      # <= 48: max-free softmax; > 48: online; > 100: clamp
+TAUS_F32 = (49.0, 150.0, 60.0, 100.0, 75.0, 49.5, 99.0, 64.0, 200.0, 50.0, 80.0, 55.0)  # fp32 selector: the gather is exact from 49
+
+
+@dataclass(frozen=True)
+class Case:
+    name: str
+    B: int
+    grid: tuple
+    heads: int
+    hd: int
+    shift: tuple
+    cell: str                  # what the row is in the table for
+
+    @property
+    def nW(self):
+        return (self.grid[0] // 16) * (self.grid[1] // 16)
+
+    @property
+    def n(self):
+        return self.grid[0] * self.grid[1]
+
+    @property
+    def items(self):           # (sample, window, head) work items, heads fastest
+        return self.B * self.nW * self.heads
+
+    @property
+    def dim(self):
+        return self.heads * self.hd
+
+    @property
+    def seed(self):
+        return zlib.crc32(self.name.encode())
+
+    def taus(self, f32=False):
+        return (TAUS_F32 if f32 else TAUS)[:self.heads]
+
+    def scale(self, f32=False):
+        """The nn.Parameter the entries take: ln tau, un-clamped."""
+        return torch.tensor(self.taus(f32), dtype=torch.float64).log().float()
+
+    def tau_eff(self, f32=False):
+        return torch.tensor([min(t, 100.0) for t in self.taus(f32)])
+
+
+# ------------------------------------------------------------------------------------------------ the case table
+#     name           B  grid      heads hd  shift     what this row is for
+CASES = [
+    Case("below8",     1, (16, 16),  4, 88, (8, 8),   "4 items: the non-XCD branch of the item walk; the roll stays inside one window"),
+    Case("items12",    1, (32, 48),  2, 80, (0, 5),   "12 items: grid shrinks to 8, uneven eighths (1 or 2 items per workgroup); one-axis shift"),
+    Case("items20",    5, (16, 16),  4, 96, (15, 15), "20 items: grid shrinks to 16, uneven eighths; shift 15 inside a single window"),
+    Case("hd64",       1, (16, 64),  4, 64, (1, 0),   "head_dim 64: the in-kernel-norm entries run, every head_dim 80 / 88 / 96 entry refuses"),
+    Case("col32",      2, (64, 16),  4, 80, (5, 0),   "one window column, wrap-around shift on the long axis"),
+    Case("items324",   9, (48, 16), 12, 88, (5, 0),   "324 items = 8 x 40.5: ragged eighths with the full grid of 256"),
+    Case("items300",   5, (32, 48), 10, 96, (8, 8),   "300 items = 8 x 37.5: ragged eighths, head_dim 96, ten heads"),
+    Case("items288",   3, (32, 64), 12, 88, (8, 8),   "288 items on the production grid: 36 per XCD = one round of 32 + a ragged round of 4"),
+    Case("items288h80", 6, (32, 48), 8, 80, (0, 5),   "288 items at head_dim 80: ragged last round"),
+    Case("row528",    11, (16, 64), 12, 88, (15, 15), "528 items: 66 per XCD = two rounds + 2; one window row, wrap-around shift 15"),
+    Case("items576",   8, (32, 48), 12, 88, (0, 0),   "576 items: the B = 8 case of the existing tests"),
+    Case("items768",   8, (32, 64), 12, 88, (1, 0),   "768 items = three full rounds, the production grid, shift (1, 0)"),
+]
+assert len({c.name for c in CASES}) == len(CASES)
+BY_NAME = {c.name: c for c in CASES}
+
+FWD_ENTRIES = ("raw_f32", "raw_bf16", "pre_pipe", "pre_nopipe", "pre_f32", "pre_f32_pv3", "tiled", "fused", "gemm_tiled")
+BWD_ENTRIES = ("bwd", "bwd_per_item", "bwd_scaled", "bwd_qknorm", "jvp")
+
+
+def fused_k_ok(c: Case):
+    """include/swiftk.h, swiftk_qkv_attention_fused / swiftk_gemm: K = dim fills whole 64-element k-tiles or ends half-way into the
+    last one (rows then extend to its end), and is at least two k-tiles."""
+    return c.dim % 64 in (0, 32) and (c.dim + 32) // 64 >= 2
+
+
+def expected_rc(c: Case, entry: str) -> int:
+    """The return code the rules of include/swiftk.h give a row at an entry (0 = runs)."""
+    pipe_hd = c.hd in (80, 88, 96)
+    if entry in ("raw_f32", "raw_bf16", "pre_nopipe", "pre_f32", "pre_f32_pv3", "pre_pipe"):
+        return 0 if c.hd in (64, 80, 88, 96) else ESHAPE   # pre_pipe at head_dim 64 runs the per-item kernel
+    if entry == "tiled":
+        return 0 if pipe_hd else ESHAPE
+    if entry in ("fused", "gemm_tiled"):
+        return 0 if pipe_hd and fused_k_ok(c) and c.heads % 2 == 0 else ESHAPE
+    return 0 if pipe_hd else ESHAPE                        # backward and tangent kernels
+
+
+def walk(items, grid=256):
+    """Which branches of the persistent kernels' item walk a count takes (attention_pipe.hip, attn_pipe_kernel "Item order" and
+    swiftk_launch_attn_pipe; the same code in qkv_attn.hip and attention_bwd.hip): the set of labels."""
+    g = grid if items >= grid else (items & ~7 if items >= 8 else items)
+    out = set()
+    if g & 7:
+        out.add("below8")                      # istep = 1, contiguous runs
+        return out
+    if g < grid:
+        out.add("shrunk_grid")
+    if items % 8:
+        out.add("ragged_eighths")
+    nx = g // 8
+    per = [(x + 1) * items // 8 - x * items // 8 for x in range(8)]
+    if any(p % nx for p in per):
+        out.add("ragged_last_round")
+    if any(p > nx for p in per):
+        out.add("several_rounds")
+    if all(p % nx == 0 for p in per):
+        out.add("full_rounds")
+    return out
+
+
+REQUIRED_WALK = ("below8", "shrunk_grid", "ragged_eighths", "ragged_last_round", "several_rounds", "full_rounds")
+
+
+# ------------------------------------------------------------------------------------------------ index maps
+def window_index(c: Case):
+    return window_token_index(c.grid, (16, 16), c.shift)  # [nW, 256]
+
+
+def to_tokens(c: Case, xw):
+    """[B, nW, H, 256, ...] (window order) -> [B, n, H, ...] (token order, un-rolled) through the oracle's map."""
+    idx = window_index(c).reshape(-1)
+    rest = list(range(4, xw.dim()))
+    y = xw.permute(0, 1, 3, 2, *rest).reshape(xw.shape[0], c.n, xw.shape[2], *xw.shape[4:])
+    out = torch.empty_like(y)
+    out[:, idx] = y
+    return out
+
+
+def locate(c: Case, token, col, width=None):
+    """(sample-local token, column of a [.., heads * width] row) -> "window w, head h, row i, column d" for a failure message."""
+    width = width or c.hd
+    idx = window_index(c)
+    pos = (idx == token).nonzero()[0].tolist()
+    return f"window {pos[0]}, head {col // width}, row {pos[1]}, column {col % width}"
+
+
+def assemble(c: Case, q, k, v):
+    """window-order q, k, v [B, nW, H, 256, hd] -> token-order qkv [B, n, 3 * dim], per head the channels [q | k | v]."""
+    return to_tokens(c, torch.stack([q, k, v], dim=4)).reshape(c.B, c.n, 3 * c.dim)
+
+
+def thirds(c: Case, x):
+    """token-order [B, n, 3 dim] -> window-order (q, k, v) [B, nW, H, 256, hd] (the inverse of `assemble`)."""
+    idx = window_index(c).reshape(-1)
+    y = x.reshape(c.B, c.n, c.heads, 3, c.hd)[:, idx].reshape(c.B, c.nW, 256, c.heads, 3, c.hd).permute(0, 1, 3, 4, 2, 5)
+    return y[:, :, :, 0], y[:, :, :, 1], y[:, :, :, 2]
+
+
+def tiled(q, k, v):
+    """The window-tiled tensor of swiftk_gemm_qkv_tiled, [B][window][head][q|k|v][256][head_dim], built on the host."""
+    return torch.stack([q, k, v], dim=3).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ draws
+def _codes(nitems, hd, g):
+    """[nitems, 256, hd] of +-1 with max off-diagonal |cos| <= COS_CAP per item (seeded redraws of the items that miss it)."""
+    code = torch.randint(0, 2, (nitems, 256, hd), generator=g).float() * 2 - 1
+    eye = torch.eye(256, dtype=torch.bool)
+    todo = torch.arange(nitems)
+    for _ in range(200):
+        dot = torch.bmm(code[todo], code[todo].transpose(1, 2))  # integers, exact
+        bad = todo[dot.masked_fill(eye, 0).abs().amax(dim=(1, 2)).double() > COS_CAP * hd]
+        if not len(bad):
+            return code
+        code[bad] = torch.randint(0, 2, (len(bad), 256, hd), generator=g).float() * 2 - 1
+        todo = bad
+    raise AssertionError("no code set under the cos cap")
+
+
+def max_offdiag_cos(code):
+    hd = code.shape[-1]
+    flat = code.reshape(-1, 256, hd)
+    dot = torch.bmm(flat, flat.transpose(1, 2))  # integers, exact
+    return float(dot.masked_fill(torch.eye(256, dtype=torch.bool), 0).abs().max()) / hd
+
+
+def _perms(shape, g):
+    return torch.rand(*shape, 256, generator=g).argsort(dim=-1)
+
+
+def bf16_values(shape, g, exps=(-1, 0, 1, 2)):
+    """+-(1 + m / 128) 2^e: random bf16-representable values bounded away from zero."""
+    m = torch.randint(0, 128, shape, generator=g).float()
+    e = torch.tensor(exps, dtype=torch.float32)[torch.randint(0, len(exps), shape, generator=g)]
+    s = torch.randint(0, 2, shape, generator=g).float() * 2 - 1
+    return s * (1 + m / 128) * torch.exp2(e)
+
+
+def ternary(shape, g):
+    return (torch.randint(0, 3, shape, generator=g) - 1).float()
+
+
+def take(x, pi):
+    """x [..., 256, d] gathered along the token axis: out[..., i, :] = x[..., pi[..., i], :]."""
+    return x.gather(-2, pi.unsqueeze(-1).expand(*pi.shape, x.shape[-1]))
+
+
+def put(x, pi):
+    """The scatter: out[..., pi[..., i], :] = x[..., i, :]."""
+    return torch.zeros_like(x).scatter_(-2, pi.unsqueeze(-1).expand(*pi.shape, x.shape[-1]), x)
+
+
+# ------------------------------------------------------------------------------------------------ the two families
+@lru_cache(maxsize=2)
+def selector(c: Case):
+    """dict of window-order tensors: code, pi, mq, mk (magnitudes, bf16-valued in [1, 4)), v, expected `out` = v[pi]."""
+    g = torch.Generator().manual_seed(c.seed)
+    sh = (c.B, c.nW, c.heads)
+    code = _codes(c.items, c.hd, g).reshape(*sh, 256, c.hd)
+    pi = _perms(sh, g)
+    mag = lambda: (64 + torch.randint(0, 192, (*sh, 256, 1), generator=g)).float() / 64
+    v = bf16_values((*sh, 256, c.hd), g)
+    return dict(code=code, pi=pi, mq=mag(), mk=mag(), v=v, out=take(v, pi))
+
+
+@lru_cache(maxsize=2)
+def uniform(c: Case):
+    """dict of window-order tensors: q (random), k (one random vector per item, repeated), v (ternary), expected `out` = sum v / 256."""
+    g = torch.Generator().manual_seed(c.seed + 1)
+    sh = (c.B, c.nW, c.heads)
+    q = torch.randn(*sh, 256, c.hd, generator=g)
+    k = torch.randn(*sh, 1, c.hd, generator=g).expand(*sh, 256, c.hd).contiguous()
+    v = ternary((*sh, 256, c.hd), g)
+    return dict(q=q, k=k, v=v, out=(v.sum(dim=3, keepdim=True) / 256).expand_as(v).contiguous())
+
+
+def selector_v(c: Case, bits=8):
+    """The selector's v and its gather with `bits` significant bits: 8 = bf16 values; 24 = full fp32 values for the fp32 kernels;
+    16 for SWIFTK_ATTN_PV_BF16X3, whose (hi, lo) split of v carries 8 + 8 bits (include/swiftk.h) and must return them all.
+    At 16 bits one pattern is left out: a v whose hi = bf16(v) rounds UP INTO THE NEXT BINADE (fraction bits 1111111 1xxxxxxx).
+    There hi + lo cancels across a power of two inside one bf16 MFMA, and the matrix pipe's aligned add takes the wrong keys'
+    1e-11 of weight (a negative term that is floored, not rounded to nearest) for one fp32 ulp of the smaller binade: measured on
+    an MI355X, 0.09 % of the elements came back as v - 1 ulp (2^-24 relative, against the 2^-18 the header states for this
+    product).  The same happens to a v that IS a power of two (fraction all zero: 2 - 1e-11 comes back as the fp32 below 2; 119
+    of 17 M elements), so those get one unit of the 16th bit.  That is the pipe's rounding, not a routing fault; the bf16 kernels
+    hide it behind the bf16 store, the exact-fp32 P V (an FMA chain that rounds to nearest) does not show it."""
+    s = selector(c)
+    if bits == 8:
+        return s["v"], s["out"]
+    g = torch.Generator().manual_seed(c.seed + 6 + bits)
+    low = torch.randint(0, 2 ** (bits - 8), s["v"].shape, generator=g).double() / 2 ** (bits - 1)   # below the 7 fraction bits of v
+    e = torch.floor(torch.log2(s["v"].abs().double()))
+    if bits == 16:
+        top = s["v"].abs().double() / torch.exp2(e) == 2 - 2.0 ** -7                                 # fraction bits 1111111
+        low = torch.where(top & (low >= 2.0 ** -8), low - 2.0 ** -8, low)
+        pow2 = s["v"].abs().double() == torch.exp2(e)
+        low = torch.where(pow2 & (low == 0), torch.full_like(low, 2.0 ** -15), low)
+    v = (s["v"].double() + s["v"].sign().double() * low * torch.exp2(e)).float()
+    return v, take(v, s["pi"])
+
+
+def raw_qkv(c: Case, fam: str, vbits=8):
+    """token-order raw q | k | v, fp32 holding bf16 values for the selector (the kernel normalises itself)."""
+    if fam == "selector":
+        s = selector(c)
+        return assemble(c, take(s["code"], s["pi"]) * s["mq"], s["code"] * s["mk"], selector_v(c, vbits)[0])
+    u = uniform(c)
+    return assemble(c, u["q"], u["k"], u["v"])
+
+
+def prenorm_parts(c: Case, fam: str, f32=False, vbits=8):
+    """window-order (q-hat tau, k-hat, v) in fp32: what SWIFTK_EPI_QKNORM would hand over (tau clamped at 100)."""
+    tau = c.tau_eff(f32).view(1, 1, c.heads, 1, 1)
+    if fam == "selector":
+        s = selector(c)
+        return take(s["code"], s["pi"]) * (tau / math.sqrt(c.hd)), s["code"] / math.sqrt(c.hd), selector_v(c, vbits)[0]
+    u = uniform(c)
+    return u["q"] / u["q"].norm(dim=-1, keepdim=True) * tau, u["k"] / u["k"].norm(dim=-1, keepdim=True), u["v"]
+
+
+def expected_out(c: Case, fam: str, vbits=8):
+    """token-order [B, n, dim] fp32 (bf16-valued at vbits = 8)."""
+    out = selector_v(c, vbits)[1] if fam == "selector" else uniform(c)["out"]
+    return to_tokens(c, out).reshape(c.B, c.n, c.dim)
+
+
+# ------------------------------------------------------------------------------------------------ fused operands
+@lru_cache(maxsize=2)
+def fused_operands(c: Case, fam: str):
+    """x [B n, ld], W [3 dim, ld] (fp32 holding bf16 values; K = dim, ld = K + the half k-tile pad where K % 64 == 32: finite
+    non-zero in x, zero in W) and the window-order expected output [B, nW, H, 256, hd].
+    selector: see the module docstring.
+    uniform:  the first head_dim columns of x are one +-1 vector per window, the others random per token; W_k reads only the first
+              (all keys of an item coincide: an integer vector), W_q holds integers in [-2, 2] over all columns (random queries), a
+              row of W_v holds 0.5 at two of the per-token columns, so v = (x_a + x_b) / 2 is ternary and differs per token."""
+    g = torch.Generator().manual_seed(c.seed + (2 if fam == "selector" else 5))
+    K = c.dim
+    ld = K + (32 if K % 64 == 32 else 0)
+    ar = torch.arange(c.hd)
+    w = torch.zeros(c.heads, 3, c.hd, ld)
+    if fam == "selector":
+        base = _codes(c.B * c.nW, c.hd, g).reshape(c.B, c.nW, 256, c.hd)
+        sigma = _perms((c.B, c.nW, c.heads), g)                                    # [B, nW, H, 256]
+        xw = take(base.unsqueeze(2).expand(c.B, c.nW, c.heads, 256, c.hd), sigma)  # block h of window row i = base[sigma_h(i)]
+        for h in range(c.heads):
+            w[h, 0, ar, ((h + 1) % c.heads) * c.hd + ar] = 1.0
+            w[h, 1, ar, h * c.hd + ar] = 1.0
+        wv = torch.randint(-2, 3, (c.heads, c.hd, K), generator=g)
+        even = wv.abs().sum(-1) % 2 == 0                                           # make the number of odd entries per row odd
+        w0 = wv[..., 0]
+        wv[..., 0] = torch.where(even, torch.where(w0 % 2 != 0, torch.full_like(w0, 2), torch.ones_like(w0)), w0)
+        w[:, 2, :, :K] = wv.float()
+        pi = sigma.argsort(dim=-1).gather(-1, sigma.roll(-1, dims=2))              # pi_h(i) = sigma_h^-1(sigma_{h+1}(i))
+    else:
+        base, pi = None, None
+        xw = torch.randint(0, 2, (c.B, c.nW, c.heads, 256, c.hd), generator=g).float() * 2 - 1
+        xw[:, :, 0] = xw[:, :, 0, :1]                                              # block 0: the same for every token of a window
+        w[:, 1, :, :c.hd] = torch.randint(-2, 3, (c.heads, c.hd, c.hd), generator=g).float()
+        w[:, 0, :, :K] = torch.randint(-2, 3, (c.heads, c.hd, K), generator=g).float()
+        two = c.hd + torch.rand(c.heads, c.hd, K - c.hd, generator=g).argsort(-1)[..., :2]
+        w[:, 2].scatter_(-1, two, 0.5)
+    xrow = xw.permute(0, 1, 3, 2, 4).reshape(c.B, c.nW, 256, K)                    # the K columns of window row i
+    x = torch.full((c.B * c.n, ld), 3.0)
+    idx = window_index(c).reshape(-1)
+    xt = torch.empty(c.B, c.n, K)
+    xt[:, idx] = xrow.reshape(c.B, c.n, K)
+    x[:, :K] = xt.reshape(c.B * c.n, K)
+    v = torch.einsum("bwik,hck->bwhic", xrow.double(), w[:, 2, :, :K].double())
+    if fam == "selector":
+        assert float(v.abs().min()) >= 1 and float(v.abs().max()) < 2 ** 24        # odd integers
+        vb = v.float().bfloat16().float()
+        out = take(vb, pi)
+    else:
+        assert bool(((v == 0) | (v.abs() == 1)).all())
+        vb = v.float()
+        out = (vb.sum(dim=3, keepdim=True) / 256).expand_as(vb).contiguous()
+    return dict(x=x, w=w.reshape(3 * c.dim, ld), K=K, ld=ld, base=base, pi=pi, v=vb, out=out)
+
+
+def fused_expected(c: Case, fam: str):
+    return to_tokens(c, fused_operands(c, fam)["out"]).reshape(c.B, c.n, c.dim)
+
+
+# ------------------------------------------------------------------------------------------------ backward
+@lru_cache(maxsize=2)
+def selector_backward(c: Case):
+    """window-order dO (bf16 values), the exact dv = scatter of dO, and the per-element bounds of |dq|, |dk| (module docstring)."""
+    s = selector(c)
+    g = torch.Generator().manual_seed(c.seed + 3)
+    sh = (c.B, c.nW, c.heads)
+    do = bf16_values((*sh, 256, c.hd), g, exps=(-1, 0, 1))
+    tv = bf16_values((*sh, 256, c.hd), g, exps=(-1, 0, 1))                     # the tangent of v for the tangent kernel
+    dv = put(do, s["pi"])
+    gamma = c.hd * U_PIPE / (1 - c.hd * U_PIPE)
+    ds = 2 * gamma * (do.double() * s["out"].double()).abs().sum(-1, keepdim=True)     # [.., 256(i), 1] bound of |dS_i,pi(i)|
+    qh, kh, _ = prenorm_parts(c, "selector")
+    qh, kh = qh.bfloat16().double().abs(), kh.bfloat16().double().abs()
+    r2 = (1 + 2.0 ** -9) ** 2
+    dq_bound = ds * take(kh, s["pi"]) * r2
+    dk_bound = put(ds * qh, s["pi"]) * r2
+    return dict(do=do, dv=dv, dq_bound=dq_bound, dk_bound=dk_bound, tv=tv, dout=take(tv, s["pi"]))
+
+
+@lru_cache(maxsize=2)
+def uniform_backward(c: Case):
+    u = uniform(c)
+    g = torch.Generator().manual_seed(c.seed + 4)
+    do = ternary(u["v"].shape, g)
+    return dict(do=do, dv=(do.sum(dim=3, keepdim=True) / 256).expand_as(do).contiguous())
+
+
+def sent(shape, f32, device="cpu"):
+    """A buffer as raw bits, prefilled with the NaN pattern."""
+    if f32:
+        return torch.full(shape, SENT_F32, dtype=torch.int32, device=device)
+    return torch.full(shape, SENT_BF16, dtype=torch.int16, device=device)
+
+
+def to_bits(x, f32):
+    if f32:
+        return x.float().contiguous().view(torch.int32)
+    return x.float().bfloat16().contiguous().view(torch.int16)
+
+
+# ------------------------------------------------------------------------------------------------ the plain bf16 backward
+def bf16r(x):
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def backward_bf16(q, k, v, o, do):
+    """The attention backward with the roundings a bf16 matrix pipe applies, restated plainly ([.., 256, hd] fp32 operands holding
+    bf16 values; o = the stored bf16 forward output): e = bf16(exp(S - max)), P = e / l, dP = dO V^T, D = rowsum(dO o O),
+    dS = bf16(P o (dP - D)), dq = dS K, dk = dS^T Q, dv = bf16(P)^T dO."""
+    s = q @ k.transpose(-2, -1)
+    e = bf16r((s - s.amax(-1, keepdim=True)).exp())
+    p = e / e.sum(-1, keepdim=True)
+    dp = do @ v.transpose(-2, -1)
+    d = (do * o).sum(-1, keepdim=True)
+    ds = bf16r(p * (dp - d))
+    return ds @ k, ds.transpose(-2, -1) @ q, bf16r(p).transpose(-2, -1) @ do
+
+
+def item_rel_l2(got, ref):
+    """[B, nW, H, 256, hd] x 2 -> relative L2 per (sample, window, head) item, [B, nW, H] (fp64)."""
+    g, r = got.double(), ref.double()
+    return (g - r).flatten(3).norm(dim=-1) / r.flatten(3).norm(dim=-1).clamp_min(1e-30)
