@@ -681,6 +681,63 @@ typedef struct {
 int swiftk_adamw_ema_step(const swiftk_opt_chunk* chunks, int n_chunks, float* grad_flat, float* exp_avg_flat,
                           float* exp_avg_sq_flat, const swiftk_opt_hyper* hyper_host, void* stream);
 
+/*
+ * The same step of the training loop for the MARS optimizer (reference training/optimizers/mars.py:15-104 `update_fn` and
+ * :301-302 `last_grad`, between trainer.py:223-231's nan_to_num and trainer.py:244-246's EMA rule), as TWO launches and
+ * no host read-back.  The reference runs ~20 torch ops per parameter tensor and `if torch.norm(c_t) > 1.0`, a
+ * device-to-host sync per tensor.
+ *   launch 1 (one block per chunk): g <- nan_to_num(g) in place; for chunks under the MARS rule
+ *     c = g + gamma_ratio * (g - last_g) and partials[chunk] = sum c^2 (AdamW-1d chunks write 0)
+ *   launch 2 (one block per chunk): norm = sqrt(sum of the owning tensor's partials, in a fixed order: the same bits in
+ *     every block of the tensor and in every run), c *= norm > 1 ? 1 / norm : 1 (c is recomputed, not stored),
+ *       m = beta1 m + (1 - beta1) c
+ *       mars-adamw: v = beta2 v + (1 - beta2) c^2;  p -= lr (wd p + m / ((sqrt(v) / sqrt(1 - beta2^t) + eps)(1 - beta1^t)))
+ *       mars-lion:  p -= lr (wd p + sign(m))                                     (exp_avg_sq is neither read nor written)
+ *     AdamW-1d chunks: the mars-adamw formulas on g itself with the *_1d hyper-parameters and lr * lr_1d_factor;
+ *     then p_ema <- p.lerp(p_ema, ema_beta) and last_g <- g.
+ * `chunks` is a DEVICE table, one entry per <= 16384 consecutive elements of one parameter tensor, a tensor's chunks
+ * adjacent in the table; grad / exp_avg / exp_avg_sq / last_grad are flat fp32 buffers indexed by flat_off.  `partials`
+ * holds n_chunks floats of scratch (every entry is written by launch 1: no clearing, no atomics); `tensor_norms` (or NULL)
+ * receives ||c|| per tensor index (0 for AdamW-1d tensors).  `hyper_host` is read on the host and travels by value; what
+ * needs beta^t is precomputed there.  Returns SWIFTK_EINVAL before anything is launched for a NULL pointer, n_chunks <= 0,
+ * n_groups outside 1..SWIFTK_OPT_MAX_GROUPS (the table's group indices must lie below n_groups: it is a device table, so
+ * its builder checks them) or a mars_type other than the two below, SWIFTK_EALIGN for a flat buffer that does not start
+ * on a 16-byte boundary.  (mars-shampoo and amsgrad have no kernel.)
+ */
+#define SWIFTK_MARS_ADAMW 0
+#define SWIFTK_MARS_LION 1
+#define SWIFTK_MARS_RULE_MARS 0
+#define SWIFTK_MARS_RULE_ADAMW_1D 1
+typedef struct {
+    float* p;              /* parameter elements of this chunk (fp32)                         */
+    float* ema;            /* the EMA copy's elements, or NULL                                */
+    int64_t flat_off;      /* offset of the chunk in grad / exp_avg / exp_avg_sq / last_grad   */
+    int32_t n;             /* elements in the chunk                                           */
+    int32_t group;         /* optimizer.param_groups index (lr / weight_decay)                */
+    int32_t tensor;        /* index of the parameter tensor the chunk belongs to (tensor_norms) */
+    int32_t first_chunk;   /* table index of that tensor's first chunk                        */
+    int32_t tensor_chunks; /* how many chunks that tensor has                                 */
+    int32_t rule;          /* SWIFTK_MARS_RULE_MARS or SWIFTK_MARS_RULE_ADAMW_1D               */
+} swiftk_mars_chunk;
+typedef struct {
+    float neg_lr[SWIFTK_OPT_MAX_GROUPS];       /* -lr of the group (the scheduled value)            */
+    float neg_lr_1d[SWIFTK_OPT_MAX_GROUPS];    /* -lr * lr_1d_factor                                */
+    float weight_decay[SWIFTK_OPT_MAX_GROUPS];
+    float beta1, one_minus_beta1, beta2, one_minus_beta2;
+    float bias1, inv_bias2_sqrt;               /* 1 - beta1^t,  1 / sqrt(1 - beta2^t)               */
+    float beta1_1d, one_minus_beta1_1d, beta2_1d, one_minus_beta2_1d;
+    float bias1_1d, inv_bias2_sqrt_1d;         /* the same for betas_1d                             */
+    float weight_decay_1d;                     /* optimizer-level, not per group                    */
+    float gamma_ratio;                         /* gamma * beta1 / (1 - beta1)                       */
+    float eps;
+    float ema_beta;
+    int32_t mars_type;                         /* SWIFTK_MARS_ADAMW or SWIFTK_MARS_LION             */
+    int32_t n_groups;
+} swiftk_mars_hyper;
+int swiftk_mars_ema_step(const swiftk_mars_chunk* chunks, int n_chunks, float* grad_flat, float* exp_avg_flat,
+                         float* exp_avg_sq_flat, float* last_grad_flat, float* partials, float* tensor_norms,
+                         const swiftk_mars_hyper* hyper_host, void* stream);
+
 /* Bytes of scratch swiftk_swinv2_forward needs for batch B (0 on a bad model). */
 int64_t swiftk_workspace_bytes(const swiftk_model* m, int B);
 

@@ -49,6 +49,23 @@ class OptHyper(C.Structure):
                 ("bias2_sqrt", C.c_float), ("ema_beta", C.c_float), ("decoupled", C.c_int32)]
 
 
+MARS_ADAMW, MARS_LION = 0, 1
+MARS_RULE_MARS, MARS_RULE_ADAMW_1D = 0, 1
+
+
+class MarsChunk(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ema", C.c_void_p), ("flat_off", C.c_int64), ("n", C.c_int32), ("group", C.c_int32),
+                ("tensor", C.c_int32), ("first_chunk", C.c_int32), ("tensor_chunks", C.c_int32), ("rule", C.c_int32)]
+
+
+class MarsHyper(C.Structure):
+    _fields_ = ([(n, C.c_float * OPT_MAX_GROUPS) for n in ("neg_lr", "neg_lr_1d", "weight_decay")]
+                + [(n, C.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "bias1", "inv_bias2_sqrt",
+                                            "beta1_1d", "one_minus_beta1_1d", "beta2_1d", "one_minus_beta2_1d", "bias1_1d",
+                                            "inv_bias2_sqrt_1d", "weight_decay_1d", "gamma_ratio", "eps", "ema_beta")]
+                + [("mars_type", C.c_int32), ("n_groups", C.c_int32)])
+
+
 class Model(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ("dtype", "H", "W", "p1", "p2", "in_ch", "out_ch", "depth", "dim", "heads", "mlp",
@@ -134,6 +151,7 @@ _SIGS = {
     "swiftk_axpby_per_sample": ([_p, _p, _p, _p, _p, _i, _l, _p], _i),
     "swiftk_channel_axpy": ([_p, _p, _p, _p, _i, _i, _l, _p], _i),
     "swiftk_adamw_ema_step": ([_p, _i, _p, _p, _p, C.POINTER(OptHyper), _p], _i),
+    "swiftk_mars_ema_step": ([_p, _i, _p, _p, _p, _p, _p, _p, C.POINTER(MarsHyper), _p], _i),
     "swiftk_profile_gemm": ([_i, _l], _i),
     "swiftk_set_tuning": ([_i, _i], _i),
     "swiftk_get_tuning": ([_i], _i),

@@ -918,6 +918,163 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const swiftk_opt_chunk* 
     }
 }
 
+// ----------------------------------------------------------------- MARS step (optimizers/mars.py:15-104, trainer.py:223-246)
+// The whole-tensor norm of c = g + gamma_ratio (g - last_g) decides the update of every element, so the step is two
+// launches over the same chunk table: the first sanitises g and leaves one sum of squares per chunk, the second sums its
+// tensor's partials itself (<= 363 of them for the largest Swift-B weight: cheaper than a third launch, and every entry
+// of `partials` is written by launch 1, so there is nothing to clear and nothing to add atomically), recomputes c
+// (8 B of reads against 8 B of store + load) and applies moments, update, EMA rule and last_g <- g.
+// Both are streaming kernels: 16-byte accesses per lane wherever the chunk's three base addresses allow, dword ones else.
+static_assert(sizeof(swiftk_mars_chunk) == 48 && sizeof(swiftk_mars_hyper) == 4 * (3 * SWIFTK_OPT_MAX_GROUPS + 18),
+              "swift_amd/_lib.py mirrors these layouts");
+
+__device__ __forceinline__ float nan_to_num_grad(float g) {  // torch.nan_to_num(nan=0, posinf=1e5, neginf=-1e5)
+    return g != g ? 0.0f : (g == INFINITY ? 1e5f : (g == -INFINITY ? -1e5f : g));
+}
+
+__device__ __forceinline__ float mars_c(float g, float lg, float k) { return fmaf(g - lg, k, g); }
+
+// Sum over the block's 256 threads in a fixed order (butterfly inside each wave, then the four waves left to right): the
+// same bits in every thread, every block that sums the same values and every run.
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__device__ __forceinline__ bool mars_chunk_vec4(const swiftk_mars_chunk& c) {
+    return !(c.flat_off & 3) && !(((uintptr_t)c.p | (uintptr_t)c.ema) & 15);  // (the flat buffers' bases are checked on the host)
+}
+
+__global__ __launch_bounds__(256) void mars_prep_kernel(const swiftk_mars_chunk* __restrict__ chunks, float* __restrict__ g,
+                                                        const float* __restrict__ last, float* __restrict__ partials,
+                                                        float gamma_ratio) {
+    __shared__ float red[4];
+    const swiftk_mars_chunk c = chunks[blockIdx.x];
+    float* __restrict__ gc = g + c.flat_off;
+    const float* __restrict__ lc = last + c.flat_off;
+    const bool mars = c.rule == SWIFTK_MARS_RULE_MARS;
+    const int nv = mars_chunk_vec4(c) ? c.n >> 2 : 0;
+    float acc = 0.0f;
+    for (int i = threadIdx.x; i < nv; i += 256) {
+        const float4 raw = reinterpret_cast<const float4*>(gc)[i];
+        const float4 s = {nan_to_num_grad(raw.x), nan_to_num_grad(raw.y), nan_to_num_grad(raw.z), nan_to_num_grad(raw.w)};
+        // (a NaN compares unequal to its replacement, so this is "any lane changed": finite gradients cost no store)
+        if (s.x != raw.x || s.y != raw.y || s.z != raw.z || s.w != raw.w) reinterpret_cast<float4*>(gc)[i] = s;
+        if (mars) {
+            const float4 l = reinterpret_cast<const float4*>(lc)[i];
+            const float c0 = mars_c(s.x, l.x, gamma_ratio), c1 = mars_c(s.y, l.y, gamma_ratio);
+            const float c2 = mars_c(s.z, l.z, gamma_ratio), c3 = mars_c(s.w, l.w, gamma_ratio);
+            acc += (c0 * c0 + c1 * c1) + (c2 * c2 + c3 * c3);
+        }
+    }
+    for (int i = nv * 4 + threadIdx.x; i < c.n; i += 256) {
+        const float raw = gc[i], s = nan_to_num_grad(raw);
+        if (s != raw) gc[i] = s;
+        if (mars) {
+            const float ci = mars_c(s, lc[i], gamma_ratio);
+            acc += ci * ci;
+        }
+    }
+    acc = block_sum_256(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+struct mars_coef {
+    float k, scale;                  // c = (g + k (g - last_g)) * scale   (AdamW-1d: k = 0, scale = 1, so c = g)
+    float b1, omb1, b2, omb2;
+    float bias1, inv_b2s, eps;
+    float neg_lr, wd;
+    float ema_beta, omb;
+    bool adam;                       // false: lion (sign of the first moment; the second moment is not touched)
+};
+
+__device__ __forceinline__ void mars_elem(const mars_coef& q, float g, float lg, float& m, float& v, float& p) {
+    const float c = mars_c(g, lg, q.k) * q.scale;
+    m = m * q.b1 + q.omb1 * c;
+    float dir;
+    if (q.adam) {
+        v = v * q.b2 + q.omb2 * c * c;
+        dir = m / ((sqrtf(v) * q.inv_b2s + q.eps) * q.bias1);
+    } else {
+        dir = (float)(m > 0.0f) - (float)(m < 0.0f);
+    }
+    p += q.neg_lr * (p * q.wd + dir);
+}
+
+__device__ __forceinline__ float ema_lerp(const mars_coef& q, float e, float p) {  // torch's two-sided lerp, as adamw_ema_kernel
+    return q.ema_beta < 0.5f ? p + q.ema_beta * (e - p) : e - (e - p) * q.omb;
+}
+
+__global__ __launch_bounds__(256) void mars_update_kernel(const swiftk_mars_chunk* __restrict__ chunks,
+                                                          const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, float* __restrict__ last,
+                                                          const float* __restrict__ partials,
+                                                          float* __restrict__ tensor_norms, swiftk_mars_hyper h) {
+    __shared__ float red[4];
+    const swiftk_mars_chunk c = chunks[blockIdx.x];
+    const bool mars = c.rule == SWIFTK_MARS_RULE_MARS;
+    mars_coef q;
+    float norm = 0.0f;
+    if (mars) {
+        float s = 0.0f;
+        for (int i = threadIdx.x; i < c.tensor_chunks; i += 256) s += partials[c.first_chunk + i];
+        norm = sqrtf(block_sum_256(s, red));
+        q.k = h.gamma_ratio;
+        q.scale = norm > 1.0f ? 1.0f / norm : 1.0f;
+        q.b1 = h.beta1, q.omb1 = h.one_minus_beta1, q.b2 = h.beta2, q.omb2 = h.one_minus_beta2;
+        q.bias1 = h.bias1, q.inv_b2s = h.inv_bias2_sqrt;
+        q.neg_lr = h.neg_lr[c.group], q.wd = h.weight_decay[c.group];
+        q.adam = h.mars_type == SWIFTK_MARS_ADAMW;
+    } else {
+        q.k = 0.0f, q.scale = 1.0f;
+        q.b1 = h.beta1_1d, q.omb1 = h.one_minus_beta1_1d, q.b2 = h.beta2_1d, q.omb2 = h.one_minus_beta2_1d;
+        q.bias1 = h.bias1_1d, q.inv_b2s = h.inv_bias2_sqrt_1d;
+        q.neg_lr = h.neg_lr_1d[c.group], q.wd = h.weight_decay_1d;
+        q.adam = true;
+    }
+    q.eps = h.eps, q.ema_beta = h.ema_beta, q.omb = 1.0f - h.ema_beta;
+    if (tensor_norms && threadIdx.x == 0 && (int)blockIdx.x == c.first_chunk) tensor_norms[c.tensor] = norm;
+    const float* __restrict__ gc = g + c.flat_off;
+    float* __restrict__ mc = m + c.flat_off;
+    float* __restrict__ vc = v + c.flat_off;
+    float* __restrict__ lc = last + c.flat_off;
+    float* __restrict__ p = c.p;
+    float* __restrict__ e = c.ema;
+    const int nv = mars_chunk_vec4(c) ? c.n >> 2 : 0;
+    for (int i = threadIdx.x; i < nv; i += 256) {
+        const float4 gv = reinterpret_cast<const float4*>(gc)[i], lv = reinterpret_cast<const float4*>(lc)[i];
+        float4 mv = reinterpret_cast<const float4*>(mc)[i], pv = reinterpret_cast<const float4*>(p)[i];
+        float4 vv = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (q.adam) vv = reinterpret_cast<const float4*>(vc)[i];
+        mars_elem(q, gv.x, lv.x, mv.x, vv.x, pv.x);
+        mars_elem(q, gv.y, lv.y, mv.y, vv.y, pv.y);
+        mars_elem(q, gv.z, lv.z, mv.z, vv.z, pv.z);
+        mars_elem(q, gv.w, lv.w, mv.w, vv.w, pv.w);
+        reinterpret_cast<float4*>(p)[i] = pv;
+        reinterpret_cast<float4*>(mc)[i] = mv;
+        if (q.adam) reinterpret_cast<float4*>(vc)[i] = vv;
+        reinterpret_cast<float4*>(lc)[i] = gv;
+        if (e) {
+            float4 ev = reinterpret_cast<const float4*>(e)[i];
+            ev.x = ema_lerp(q, ev.x, pv.x), ev.y = ema_lerp(q, ev.y, pv.y);
+            ev.z = ema_lerp(q, ev.z, pv.z), ev.w = ema_lerp(q, ev.w, pv.w);
+            reinterpret_cast<float4*>(e)[i] = ev;
+        }
+    }
+    for (int i = nv * 4 + threadIdx.x; i < c.n; i += 256) {
+        const float gi = gc[i];
+        float mi = mc[i], vi = q.adam ? vc[i] : 0.0f, pi = p[i];
+        mars_elem(q, gi, lc[i], mi, vi, pi);
+        p[i] = pi;
+        mc[i] = mi;
+        if (q.adam) vc[i] = vi;
+        lc[i] = gi;
+        if (e) e[i] = ema_lerp(q, e[i], pi);
+    }
+}
+
 }  // namespace
 
 int g_modnorm_bwd_fused = 1;  // tuning key 16 (A/B): 0 = row pass and column pass as two kernels
@@ -1231,6 +1388,28 @@ extern "C" int swiftk_adamw_ema_step(const swiftk_opt_chunk* chunks, int n_chunk
     if (!chunks || !grad_flat || !exp_avg_flat || !exp_avg_sq_flat || !hyper_host || n_chunks <= 0) return SWIFTK_EINVAL;
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), chunks, grad_flat,
                        exp_avg_flat, exp_avg_sq_flat, *hyper_host);
+    SWIFTK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int swiftk_mars_ema_step(const swiftk_mars_chunk* chunks, int n_chunks, float* grad_flat, float* exp_avg_flat,
+                                    float* exp_avg_sq_flat, float* last_grad_flat, float* partials, float* tensor_norms,
+                                    const swiftk_mars_hyper* hyper_host, void* stream) {
+    if (!chunks || !grad_flat || !exp_avg_flat || !exp_avg_sq_flat || !last_grad_flat || !partials || !hyper_host ||
+        n_chunks <= 0)
+        return SWIFTK_EINVAL;
+    const swiftk_mars_hyper h = *hyper_host;
+    if (h.n_groups < 1 || h.n_groups > SWIFTK_OPT_MAX_GROUPS) return SWIFTK_EINVAL;
+    if (h.mars_type != SWIFTK_MARS_ADAMW && h.mars_type != SWIFTK_MARS_LION) return SWIFTK_EINVAL;
+    // the 16-byte path of both kernels indexes the flat buffers from their bases
+    if (((uintptr_t)grad_flat | (uintptr_t)exp_avg_flat | (uintptr_t)exp_avg_sq_flat | (uintptr_t)last_grad_flat) & 15)
+        return SWIFTK_EALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(mars_prep_kernel, dim3(n_chunks), dim3(256), 0, st, chunks, grad_flat, last_grad_flat, partials,
+                       h.gamma_ratio);
+    SWIFTK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mars_update_kernel, dim3(n_chunks), dim3(256), 0, st, chunks, grad_flat, exp_avg_flat, exp_avg_sq_flat,
+                       last_grad_flat, partials, tensor_norms, h);
     SWIFTK_CHECK_LAUNCH();
     return 0;
 }

@@ -258,7 +258,7 @@ class Trainer:
         self.total_kimg, self.ema_halflife_kimg, self.ema_rampup_ratio = total_kimg, ema_halflife_kimg, ema_rampup_ratio
         self.kimg_per_tick, self.checkpoint_ticks = kimg_per_tick, checkpoint_ticks
         self.global_batch_size = None
-        self._fused = None  # FusedAdamEMA once the flat gradient buffer exists (False: optimiser not covered)
+        self._fused = None  # FusedAdamEMA / FusedMarsEMA once the flat gradient buffer exists (False: optimiser not covered)
         from .profiling import StepProfiler, _NoProfiler
         self.prof = StepProfiler() if profile else _NoProfiler()  # trainer.py:155-177
 
@@ -288,7 +288,7 @@ class Trainer:
                 g["lr"] = lo + 0.5 * (base - lo) * (1 + math.cos(math.pi * prog))
 
     def _fused_optim(self, flat):
-        """Adam / AdamW on device parameters: the whole step (sanitise, update, EMA) is one HIP kernel."""
+        """Adam / AdamW (one HIP kernel) or MARS (two) on device parameters: the whole step -- sanitise, update, EMA."""
         if self._fused is None:
             from . import fused_optim
             self._fused = False
@@ -297,7 +297,7 @@ class Trainer:
                 ema_of = {n: e for n, e in self.ema.named_parameters()}
                 ema_p = [ema_of[n] for n, p in self.net.named_parameters() if p.requires_grad]
                 if len(net_p) == len(list(self.net.parameters())):  # (a frozen parameter would still need its EMA lerp)
-                    self._fused = fused_optim.FusedAdamEMA(self.optimizer, net_p, ema_p, flat)
+                    self._fused = fused_optim.make(self.optimizer, net_p, ema_p, flat)
         return self._fused
 
     def _backward_step(self, global_nimg: int, loss: torch.Tensor):

@@ -502,12 +502,8 @@ def fx_metrics_tiny():
     save("metrics_tiny", pred=pred, y=y, lat=lat, keys=np.array(sorted(out)), values=np.array([out[k] for k in sorted(out)]))
 
 
-
-def fx_trainer_tiny():
-    """The reference's optimisation step itself -- ``Trainer._backward_step`` (training/trainer.py:199-247): LR warm-up /
-    cosine schedule, ``nan_to_num`` gradient sanitising, AdamW step, EMA rule -- called unbound on a stand-in ``self`` (the
-    constructor needs ezpz / DDP; the step does not).  Gradients are injected through a loss that is linear in the
-    parameters, NaN / +-inf entries included.  Import-time stubs: xarray, mpi4py, torchinfo, swift.utils.io, ezpz.History."""
+def _ref_trainer_cls():
+    """The reference's Trainer class behind its import-time stubs: xarray, mpi4py, torchinfo, swift.utils.io, ezpz.History."""
     import torch._dynamo  # noqa: F401  (the optimiser imports it lazily, and its module scan trips over spec-less stubs)
     for name in ("xarray", "torchinfo"):
         sys.modules.setdefault(name, types.ModuleType(name))
@@ -521,6 +517,15 @@ def fx_trainer_tiny():
     ez.get_rank, ez.get_world_size = (lambda: 0), (lambda: 1)
     ez.History = type("History", (), {})
     from swift.training.trainer import Trainer
+    return Trainer
+
+
+def fx_trainer_tiny():
+    """The reference's optimisation step itself -- ``Trainer._backward_step`` (training/trainer.py:199-247): LR warm-up /
+    cosine schedule, ``nan_to_num`` gradient sanitising, AdamW step, EMA rule -- called unbound on a stand-in ``self`` (the
+    constructor needs ezpz / DDP; the step does not).  Gradients are injected through a loss that is linear in the
+    parameters, NaN / +-inf entries included.  Import-time stubs: xarray, mpi4py, torchinfo, swift.utils.io, ezpz.History."""
+    Trainer = _ref_trainer_cls()
     torch.manual_seed(0)
     shapes = {"model.pos_embed": (1, 6, 8), "model.layers.0.w1.weight": (16, 8), "model.layers.0.norm.norm.weight": (8,),
               "model.layers.0.norm.norm.bias": (8,), "model.layers.0.norm.modulation.weight": (16, 8), "model.head.weight": (4, 8)}
@@ -753,7 +758,115 @@ def fx_edm_tiny():
          **{f"ren{i}": r for i, r in enumerate(ren)}, grad_keys=np.array(gsel), w_lat=L.w_lat, w_var=L.w_var, **out)
 
 
-ALL = dict(edm_tiny=fx_edm_tiny, swiftb_fp64=fx_swiftb_fp64, swiftb_2s_bf16=fx_swiftb_2s_bf16, scm_distill_tiny=fx_scm_distill_tiny, index_streams=fx_index_streams, era5_tiny=fx_era5_tiny, swiftb_long=fx_swiftb_long, trainer_tiny=fx_trainer_tiny, metrics_tiny=fx_metrics_tiny, val_tiny=fx_val_tiny, muon_tiny=fx_muon_tiny, swinv2_tiny=fx_swinv2_tiny, swinv2_smallb=fx_swinv2_smallb, attention_hd88=fx_attention_hd88,
+def fx_mars_tiny():
+    """The reference's MARS (training/optimizers/mars.py) inside its ``Trainer._backward_step`` on the stand-in ``self`` of
+    ``fx_trainer_tiny``: LR schedule, ``nan_to_num``, optimizer, EMA.  Four steps, three configurations (mars-adamw,
+    mars-lion, mars-adamw with optimize_1d), two param groups.  Every 2-D tensor sees two large-gradient steps (std 0.5) and
+    two small ones (std 0.004 - 0.02) in a row, so that ``||c_t||`` lies on both sides of 1 (the step after a large gradient
+    is clipped whatever its own scale: ``c_t`` carries 0.475 of the previous gradient); the norms are recorded, and none may
+    lie near 1, where a rounding difference would pick the other branch.  Arrays and names only."""
+    Trainer = _ref_trainer_cls()
+    import swift.training.optimizers.mars as ref_mars
+    shapes = {"model.pos_embed": (1, 6, 8), "model.layers.0.w1.weight": (16, 8), "model.layers.0.norm.norm.weight": (32,),
+              "model.layers.0.norm.norm.bias": (32,), "model.layers.0.norm.modulation.weight": (16, 8),
+              "model.layers.0.w2.weight": (96, 64), "model.head.weight": (4, 8)}
+    names = list(shapes)
+    # (std per step): large-large-small-small or the reverse for the matrices, always large for the others
+    sched = {"model.layers.0.w1.weight": (0.5, 0.5, 0.02, 0.01), "model.layers.0.norm.modulation.weight": (0.01, 0.02, 0.5, 0.5),
+             "model.layers.0.w2.weight": (0.5, 0.5, 0.004, 0.004), "model.head.weight": (0.02, 0.004, 0.5, 0.5)}
+    no_decay = [i for i, n in enumerate(names) if "pos_embed" in n or ("norm" in n and "modulation" not in n)]
+    nimgs = [2, 4, 10, 20]
+    def grads(st, lion):
+        gs = [det_normal(shapes[n], 300 + st, n, std=sched.get(n, (0.5,) * 4)[st]) for n in names]
+        # +-inf where the tensor's gradients are large anyway; NaN (-> 0) only once exp_avg is non-zero.  Under mars-lion the
+        # matrices get no +-inf: 1e5 in one entry leaves every other entry of exp_avg below 1e-5 of the maximum
+        if st == 0 and not lion:
+            gs[1].view(-1)[5] = float("inf")
+            gs[5].view(-1)[700] = float("-inf")
+        if st == 1:
+            gs[1].view(-1)[3] = float("nan")
+            gs[2].view(-1)[1] = float("nan")
+            gs[5].view(-1)[4097] = float("nan")
+        if st == 3:
+            if not lion:
+                gs[4].view(-1)[0] = float("-inf")
+            gs[0].view(-1)[7] = float("inf")
+            gs[3].view(-1)[2] = float("-inf")
+        return gs
+
+    G = [grads(st, False) for st in range(len(nimgs))]
+    out = {"names": np.array(names), "no_decay": np.array(no_decay), "nimgs": np.array(nimgs)}
+    for st, gs in enumerate(G):
+        for n, g in zip(names, gs):
+            out[f"g{st}_{n}"] = g
+    configs = {"adamw": dict(mars_type="mars-adamw"), "lion": dict(mars_type="mars-lion"),
+               "adamw1d": dict(mars_type="mars-adamw", optimize_1d=True)}
+    out["configs"] = np.array(list(configs))
+    real_norm = torch.norm
+    for cfg, kw in configs.items():
+        net = torch.nn.ParameterList([torch.nn.Parameter(det_normal(sh, 31, k, std=0.3)) for k, sh in shapes.items()])
+        ema = torch.nn.ParameterList([torch.nn.Parameter(v.detach().clone() + 0.01, requires_grad=False) for v in net])
+        params = list(net.parameters())
+        groups = [{"params": [p for i, p in enumerate(params) if i not in no_decay], "weight_decay": 0.05},
+                  {"params": [params[i] for i in no_decay], "weight_decay": 0.0, "lr": 1e-3}]
+        opt = ref_mars.MARS(groups, lr=2e-3, lr_1d=3e-3, weight_decay_1d=0.1, **kw)
+        me = types.SimpleNamespace(lr_rampup_kimg=0.004, optimizer=opt, base_lr=[g["lr"] for g in opt.param_groups],
+                                   lr_min_factor=0.01, lr_cosine_anneal=True, total_kimg=0.02,
+                                   scaler=torch.amp.GradScaler("cpu", enabled=False), net=net, ema=ema, ema_halflife_kimg=0.5,
+                                   ema_rampup_ratio=0.05, global_batch_size=2)
+        if cfg == "adamw":
+            for k, v in zip(names, params):
+                out[f"p0_{k}"] = v.detach().clone()
+            for k, v in zip(names, ema.parameters()):
+                out[f"e0_{k}"] = v.detach().clone()
+        seen = []
+        lion = kw["mars_type"] == "mars-lion"
+        for st, nimg in enumerate(nimgs):
+            opt.zero_grad(set_to_none=True)
+            Gs = grads(st, lion)
+            for n, g, g_all in zip(names, Gs, G[st]):  # (only what differs from the shared gradients is stored again)
+                if not torch.equal(torch.nan_to_num(g, nan=7.0), torch.nan_to_num(g_all, nan=7.0)):
+                    out[f"{cfg}_g{st}_{n}"] = g
+            loss = sum((p * g).sum() for p, g in zip(params, Gs))
+            rec = []
+            torch.norm = lambda x, *a, **k: (rec.append(real_norm(x, *a, **k)), rec[-1])[1]  # update_fn: torch.norm(c_t)
+            try:
+                Trainer._backward_step(me, nimg, loss)
+            finally:
+                torch.norm = real_norm
+            # update_fn is called in param_groups order, and takes the norm only under the MARS rule
+            order = [p for g in opt.param_groups for p in g["params"]]
+            name_of = {id(p): n for n, p in zip(names, params)}
+            ruled = [name_of[id(p)] for p in order if kw.get("optimize_1d") or p.ndim == 2]
+            assert len(rec) == len(ruled)
+            for n, v in zip(ruled, rec):
+                out[f"{cfg}_norm{st}_{n}"] = np.float64(v)
+                seen.append(float(v))
+            out[f"{cfg}_lr_{st}"] = np.array([g["lr"] for g in opt.param_groups])
+            for n, p, e in zip(names, params, ema.parameters()):
+                out[f"{cfg}_p{st + 1}_{n}"] = p.detach().clone()
+                if st in (0, len(nimgs) - 1):
+                    out[f"{cfg}_e{st + 1}_{n}"] = e.detach().clone()
+            if lion:  # where the sign of exp_avg is the update, a rounding difference must not be able to flip it
+                for n, p in zip(names, params):
+                    if n not in ruled:
+                        continue
+                    m = opt.state[p]["exp_avg"].abs()
+                    assert float(m.min()) >= 1e-5 * float(m.max()), (cfg, st, n, float(m.min()), float(m.max()))
+        assert any(v > 1.0 for v in seen) and any(v < 1.0 for v in seen), (cfg, seen)
+        assert all(abs(v - 1.0) > 0.05 for v in seen), (cfg, sorted(seen, key=lambda v: abs(v - 1.0))[:3])
+        print(f"  {cfg}: {sum(v > 1 for v in seen)} clipped, {sum(v < 1 for v in seen)} unclipped; closest to 1: "
+              f"{min(seen, key=lambda v: abs(v - 1.0)):.4f}")
+        for n, p in zip(names, params):   # the optimizer state a checkpoint would carry (last_grad is g3, sanitised)
+            out[f"{cfg}_m4_{n}"] = opt.state[p]["exp_avg"].detach().clone()
+            if cfg == "adamw":
+                out[f"{cfg}_v4_{n}"] = opt.state[p]["exp_avg_sq"].detach().clone()
+        out[f"{cfg}_state_keys"] = np.array(sorted(opt.state[params[0]].keys()))
+        out[f"{cfg}_group_keys"] = np.array(sorted(k for k in opt.param_groups[0] if k != "params"))
+    save("mars_tiny", **out)
+
+
+ALL = dict(mars_tiny=fx_mars_tiny, edm_tiny=fx_edm_tiny, swiftb_fp64=fx_swiftb_fp64, swiftb_2s_bf16=fx_swiftb_2s_bf16, scm_distill_tiny=fx_scm_distill_tiny, index_streams=fx_index_streams, era5_tiny=fx_era5_tiny, swiftb_long=fx_swiftb_long, trainer_tiny=fx_trainer_tiny, metrics_tiny=fx_metrics_tiny, val_tiny=fx_val_tiny, muon_tiny=fx_muon_tiny, swinv2_tiny=fx_swinv2_tiny, swinv2_smallb=fx_swinv2_smallb, attention_hd88=fx_attention_hd88,
            samplers_tiny=fx_samplers_tiny, rollout_tiny=fx_rollout_tiny, losses_tiny=fx_losses_tiny,
            swiftb_step=fx_swiftb_step, weights_aux=fx_weights_aux)
 

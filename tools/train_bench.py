@@ -15,7 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8); ap.add_argument("--steps", type=int, default=4)
 ap.add_argument("--iters", type=int, default=6); ap.add_argument("--depth", type=int, default=12)
 ap.add_argument("--loss", default="crps", choices=["crps", "scm", "trigflow"])
-ap.add_argument("--opt", default="adamw", choices=["adamw", "muon"])
+ap.add_argument("--opt", default="adamw", choices=["adamw", "muon", "mars"])
 ap.add_argument("--dim", type=int, default=1056); ap.add_argument("--heads", type=int, default=12)  # 1280 / 16, 1536 / 16: the larger variants
 ap.add_argument("--grad-digest", default=None, help="write per-parameter gradient norms of the first and the last iteration here (JSON)")
 ap.add_argument("--dist", type=int, default=1, help="1: run the gradient collectives for real (a one-rank RCCL group unless launched "
@@ -52,6 +52,10 @@ if a.opt == "muon":  # the sCM experiment's optimiser (train.py:286-309 paramete
     ap_ = [p for n, p in net.named_parameters() if not (p.ndim >= 2 and "transformer" in n)]
     opt = MuonWithAuxAdam([dict(params=mp, use_muon=True, lr=0.02, weight_decay=0.01),
                            dict(params=ap_, use_muon=False, lr=3e-4, betas=(0.9, 0.95), weight_decay=0.01, eps=1e-10)])
+elif a.opt == "mars":  # configs/optimizer/mars.yaml over net.parameters(), as swift_amd/train.py builds it (a smaller lr for the seeded weights)
+    from swift_amd.training.optimizers.mars import MARS
+    MARS_KW = dict(mars_type="mars-adamw", lr=1e-5, lr_1d=1e-5, weight_decay=0.1)
+    opt = MARS(net.parameters(), **MARS_KW)
 else:
     opt = torch.optim.AdamW(adamw_param_groups(net, 1e-5), lr=1e-5, betas=(0.9, 0.95), eps=1e-6)
 noise = dict(dist="loguniform", sigma_min=0.02, sigma_max=200.0)
@@ -159,6 +163,70 @@ def _fwd_flop(dim, depth):  # one network evaluation of one sample (SURVEY.md se
     layer = 2 * ntok * (dim * 3 * dim + dim * dim + dim * 2 * mlp + mlp * dim) + 4 * ntok * 256 * dim + 2 * 2 * dim * 2 * dim
     return 2 * ntok * 564 * dim + depth * layer + 2 * ntok * dim * 276
 FWD = _fwd_flop(a.dim, a.depth) if a.dim != 1056 else 2.7535e12 * a.depth / 12
+def optimizer_step_times(reps=10):
+    """HIP-event times of the optimisation step alone at this model's size, all in this process: the fused MARS step the trainer
+    ran (swiftk_mars_ema_step), the same optimizer as the torch-op class on separately allocated gradients (the reference's
+    sequence: nan_to_num per gradient, ~20 ops and one host sync per tensor, lerp per EMA tensor), and swiftk_adamw_ema_step."""
+    from swift_amd.training import fused_optim
+    HBM = 6.29e12  # measured float4-copy rate (MI355X_MICROARCH.md)
+
+    def timed(fn):
+        fn()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+        for e0, e1 in ev:
+            e0.record()
+            fn()
+            e1.record()
+        torch.cuda.synchronize()
+        return sorted(e0.elapsed_time(e1) for e0, e1 in ev)[reps // 2]
+
+    flat = tr.ddp.flatten_grads()
+    n = flat.numel()
+    out = {"parameters": n, "tensors": len(list(net.parameters())), "reps": reps, "hbm_rate_TBps": HBM / 1e12}
+
+    def record(name, ms, bytes_per_param):
+        out[name] = {"ms": ms, "bytes_per_parameter": bytes_per_param,
+                     "hbm_frac": None if bytes_per_param is None else bytes_per_param * n / (ms * 1e-3) / HBM}
+
+    # launch 1 reads g and last_grad (g is stored back only where nan_to_num changed it): 8 B; launch 2 reads g, last_grad,
+    # exp_avg, exp_avg_sq, p, p_ema and writes all but g: 44 B
+    record("mars_fused", timed(lambda: tr._fused.step(0.999)), 52)
+    P2 = [torch.nn.Parameter(p.detach().clone()) for p in net.parameters()]
+    E2 = [e.detach().clone() for e in tr.ema.parameters()]
+    for p2, p in zip(P2, net.parameters()):
+        p2.grad = p.grad.detach().clone()
+    o2 = MARS(P2, **MARS_KW)
+
+    def torch_ops():
+        for p2 in P2:
+            torch.nan_to_num(p2.grad, nan=0, posinf=1e5, neginf=-1e5, out=p2.grad)
+        o2.step()
+        with torch.no_grad():
+            torch._foreach_copy_(E2, torch._foreach_lerp([q.detach() for q in P2], E2, 0.999))
+
+    record("mars_torch_ops", timed(torch_ops), None)
+    del o2, E2
+    for p2 in P2:
+        p2.grad = None
+    f3 = flat.clone()
+    o = 0
+    for p2 in P2:
+        p2.grad = f3[o:o + p2.numel()].view_as(p2)
+        o += p2.numel()
+    o3 = torch.optim.AdamW(P2, lr=1e-5, betas=(0.9, 0.95), eps=1e-6, weight_decay=1e-5)
+    E3 = [p2.detach().clone() for p2 in P2]
+    fa = fused_optim.FusedAdamEMA(o3, P2, E3, f3)
+    record("adamw_fused", timed(lambda: fa.step(0.999)), 36)
+    out["mars_over_adamw"] = out["mars_fused"]["ms"] / out["adamw_fused"]["ms"]
+    out["byte_ratio"] = 52 / 36
+    out["torch_ops_over_fused"] = out["mars_torch_ops"]["ms"] / out["mars_fused"]["ms"]
+    return out
+
+
+OPT_STEP = None
+if a.opt == "mars" and getattr(tr, "_fused", None):
+    OPT_STEP = optimizer_step_times()
+    print("optimizer step alone (HIP events, median): " + json.dumps(OPT_STEP), file=sys.stderr)
 AR = {}
 if a.dist:
     tr.ddp.calibrate_serial()
@@ -167,7 +235,8 @@ if a.dist:
                   "compute stream waited for the collectives in sync() per iteration, overlap_frac = 1 - exposed / serial; a one-rank group "
                   "measures the call path, not xGMI")
 _dumps = json.dumps
-json.dumps = lambda rec, *aa, **kk: _dumps(dict(rec, allreduce=AR) if isinstance(rec, dict) and "metric" in rec else rec, *aa, **kk)
+json.dumps = lambda rec, *aa, **kk: _dumps(dict(rec, allreduce=AR, **({"optimizer_step": OPT_STEP} if OPT_STEP else {}))
+                                          if isinstance(rec, dict) and "metric" in rec else rec, *aa, **kk)
 fused = bool(getattr(tr, "_fused", None))
 if a.loss == "trigflow":  # TrigFlowLoss (loss.py:117-160): one forward, one backward (2x) per sample
     fl = 3 * a.batch * FWD
