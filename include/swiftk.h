@@ -423,7 +423,7 @@ int swiftk_swiglu_bwd(const void* h, int64_t ldh, const void* dout, int64_t ldo,
 
 /* Backward of swiftk_modnorm_residual's norm branch: g = dL/d(out) fp32 [M, d] -> dy (dtype), and fp32 atomic sums
  * dgamma[d], dbeta[d], dmod[B, lddmod] (scale grads at [0,d), shift grads at [d,2d)); the residual branch is identity.
- * row_stats: caller-provided scratch of 2*M floats (per-row mean and 1/std, handed from the row pass to the column pass; the
+ * row_stats: caller-provided scratch of 2*M floats (per-row mean of y - y[row][0] and 1/std, handed from the row pass to the column pass; the
  * one-kernel form -- rows_per_sample a multiple of 64 and >= d -- keeps its per-sample column sums [2][B][d] there instead). */
 int swiftk_modnorm_bwd(const void* y, int64_t ldy, const float* g, void* dy, int64_t lddy, const float* gamma,
                        const float* beta, const float* mod, int64_t ldmod, float* dgamma, float* dbeta, float* dmod,
@@ -440,7 +440,10 @@ int swiftk_modnorm_bwd_ws0(const void* y, int64_t ldy, const float* g, void* dy,
 /* Backward of SWIFTK_EPI_QKNORM: qkvh / dqkvh [M, ld] (normalised values and their gradients), rn [M, 3*heads] the
  * 1/max(|.|,1e-12) factors the epilogue stored through ep1 -> dqkv [M, ldo] (raw projections), dscale[heads] += .
  * In place: dqkvh == dqkv (row stride ldo; the attention backward wrote straight into the next GEMM's operand buffer) --
- * v's gradient passes through unchanged, so only the q-hat / k-hat vectors are read and rewritten (2/3 of the vectors). */
+ * v's gradient passes through unchanged, so only the q-hat / k-hat vectors are read and rewritten (2/3 of the vectors).
+ * Limits: a head vector is <= 16 whole 16-byte chunks -- head_dim % 8 == 0 and <= 128 in bf16, head_dim % 4 == 0 and <= 64 in
+ * fp32 -- heads <= 64, ld and ldo >= 3 * heads * head_dim (SWIFTK_ESHAPE otherwise); qkvh, dqkvh, dqkv and every row of them on a
+ * 16-byte boundary (SWIFTK_EALIGN).  A refused call writes nothing. */
 int swiftk_qknorm_bwd(const void* qkvh, const void* dqkvh, int64_t ld, const float* rn, void* dqkv, int64_t ldo,
                       const float* scale, float* dscale, int64_t M, int heads, int head_dim, int dtype, void* stream);
 /* Both in one call (round 4): dqkv [tokens, ldd] <- the gradient w.r.t. the RAW to_qkv output (the operand of the to_qkv data- and

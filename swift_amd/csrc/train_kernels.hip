@@ -115,6 +115,14 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------ SwiGLU (unfused form)
 // h [M, 2*mlp] with columns interleaved (gate_j, up_j) -> hmid[m][j] = silu(gate) * up   (swinv2.py:99-100)
+// sigmoid at the precision of the result type: for bf16 results the hardware exp and reciprocal (__expf rounds its argument
+// g log2(e) once, an error of 4e-8 |g| relative to exp(-g): 1.3e-6 at g = -30, far below the 2^-9 of the bf16 rounding that
+// follows); fp32 results take expf and an IEEE division -- these kernels are bound by their memory traffic either way
+template <typename T>
+__device__ __forceinline__ float sigmoid_for(float g) {
+    if constexpr (sizeof(T) == 4) return 1.0f / (1.0f + expf(-g));
+    else return __builtin_amdgcn_rcpf(1.0f + __expf(-g));
+}
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ h, int64_t ldh, T* __restrict__ o, int64_t ldo,
                                                          int64_t M, int mlp) {
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ h
         const int64_t m = i / mlp;
         const int j = (int)(i - m * mlp);
         const float g = ldf(h + m * ldh + 2 * j), u = ldf(h + m * ldh + 2 * j + 1);
-        o[m * ldo + j] = elem<T>::from_f(g * __builtin_amdgcn_rcpf(1.0f + __expf(-g)) * u);
+        o[m * ldo + j] = elem<T>::from_f(g * sigmoid_for<T>(g) * u);
     }
 }
 // dh[m][2j] = dho * up * (s + g s (1-s)),  dh[m][2j+1] = dho * g s,   s = sigmoid(gate)
@@ -135,7 +143,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ h
         const int64_t m = i / mlp;
         const int j = (int)(i - m * mlp);
         const float g = ldf(h + m * ldh + 2 * j), u = ldf(h + m * ldh + 2 * j + 1), d = ldf(dho + m * ldo + j);
-        const float s = __builtin_amdgcn_rcpf(1.0f + __expf(-g));
+        const float s = sigmoid_for<T>(g);
         dh[m * lddh + 2 * j] = elem<T>::from_f(d * u * (s + g * s * (1.0f - s)));
         dh[m * lddh + 2 * j + 1] = elem<T>::from_f(d * g * s);
     }
@@ -177,10 +185,21 @@ __global__ __launch_bounds__(256) void modnorm_bwd_rows_kernel(const T* __restri
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] = dn[i][e] = 0.f;
         }
+    }
+    // the statistics of t = y - y0 (y0 = the row's first element), as the one-kernel form below: a row with a common offset far
+    // larger than its spread (300 +- 0.02) otherwise loses the offset's rounding errors in the sum, 1.6e-3 of the spread, in
+    // its mean -- and with it in every n this row adds to the column sums
+    const float y0 = __shfl(v[0][0], 0, 64);
+#pragma unroll
+    for (int i = 0; i < SLOTS; ++i) {
+        if (lane + 64 * i < nc) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[i][e] -= y0;
+        }
         sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }
     const float inv_d = 1.0f / (float)d;
-    const float mean = wave_sum(sum) * inv_d;
+    const float mean = wave_sum(sum) * inv_d;  // of t
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < SLOTS; ++i)
@@ -210,7 +229,7 @@ __global__ __launch_bounds__(256) void modnorm_bwd_rows_kernel(const T* __restri
                    rstd * (dn[i][2] - s1 - v[i][2] * s2), rstd * (dn[i][3] - s1 - v[i][3] * s2));
     }
     if (lane == 0) {
-        stats[2 * row] = mean;
+        stats[2 * row] = mean;  // (of y - y0: the column pass subtracts y0 itself, y0 + mean would round at the offset's size)
         stats[2 * row + 1] = rstd;
     }
 }
@@ -410,10 +429,10 @@ __global__ __launch_bounds__(256) void modnorm_bwd_cols_kernel(const T* __restri
             float v[4], gg[4];
             ld4<T>(y + row * ldy + 4 * c, v);
             ld4<float>(g + row * d + 4 * c, gg);
-            const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+            const float mean = stats[2 * row], rstd = stats[2 * row + 1], y0 = ldf(y + row * ldy);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float n = (v[e] - mean) * rstd;
+                const float n = ((v[e] - y0) - mean) * rstd;
                 const float dl = gg[e] * (1.0f + sc[e]);
                 acc[e] += dl * n;
                 acc[4 + e] += dl;
@@ -720,25 +739,50 @@ __global__ __launch_bounds__(256) void trigflow_prep_kernel(const float* __restr
     }
 }
 // loss = 1/(B H W) sum [ exp(-lv_b) w (sd F - v)^2 + lv_b ];  dF, dlv optional
+// dlogvar[b] is summed like the loss value: in the lane while the wave's 64 consecutive elements stay inside one sample, over
+// the wave when they move to the next one (the grid-stride walk only moves forward, so <= B times), then one atomic per wave
+// and sample.  An atomic per element -- 2.26 M single-precision adds onto one address per sample at 69 x 128 x 256, each rounded
+// against the running total -- left dlogvar 4e-3 off (measured) and serialised the kernel; only the elements of a wave that straddles two
+// samples still go one by one.  The loop runs on the wave's first index so that every lane reaches the wave sums.
 __global__ __launch_bounds__(256) void trigflow_loss_kernel(const float* __restrict__ F, const float* __restrict__ vt,
                                                             const float* __restrict__ logvar, const float* __restrict__ w_var,
                                                             const float* __restrict__ w_lat, float* __restrict__ loss,
                                                             float* __restrict__ dF, float* __restrict__ dlogvar, float sd,
                                                             int64_t n, int C, int H, int W, float gscale, float inv_bhw) {
-    float acc = 0.f;
+    float acc = 0.f, dacc = 0.f;  // dacc: this lane's share of dlogvar[db]
+    int64_t db = -1;
     const int64_t per_sample = (int64_t)C * H * W;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int h = (int)((i / W) % H), c = (int)((i / ((int64_t)W * H)) % C);
-        const int64_t b = i / per_sample;
-        const float lv = logvar ? logvar[b] : 0.f, iv = expf(-lv);
-        const float w = w_var[c] * w_lat[h];
-        const float r = sd * F[i] - vt[i];
-        acc += iv * w * r * r + lv;
-        if (dF) dF[i] = gscale * inv_bhw * 2.0f * sd * iv * w * r;
-        if (dlogvar) atomicAdd(dlogvar + b, gscale * inv_bhw * (1.0f - iv * w * r * r));
+    const int lane = threadIdx.x & 63;
+    for (int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x - lane); i0 < n; i0 += (int64_t)gridDim.x * 256) {
+        const int64_t i = i0 + lane;
+        const int64_t b0 = i0 / per_sample, b1 = min(i0 + 63, n - 1) / per_sample;  // (wave-uniform)
+        if (dlogvar && b0 != db) {
+            dacc = wave_sum(dacc);
+            if (lane == 0 && db >= 0) atomicAdd(dlogvar + db, dacc);
+            dacc = 0.f;
+            db = b0;
+        }
+        if (i < n) {
+            const int h = (int)((i / W) % H), c = (int)((i / ((int64_t)W * H)) % C);
+            const int64_t b = i / per_sample;
+            const float lv = logvar ? logvar[b] : 0.f, iv = expf(-lv);
+            const float w = w_var[c] * w_lat[h];
+            const float r = sd * F[i] - vt[i];
+            acc += iv * w * r * r + lv;
+            if (dF) dF[i] = gscale * inv_bhw * 2.0f * sd * iv * w * r;
+            if (dlogvar) {
+                const float t = gscale * inv_bhw * (1.0f - iv * w * r * r);
+                if (b0 == b1) dacc += t;
+                else atomicAdd(dlogvar + b, t);
+            }
+        }
+    }
+    if (dlogvar && db >= 0) {
+        dacc = wave_sum(dacc);
+        if (lane == 0) atomicAdd(dlogvar + db, dacc);
     }
     acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) atomicAdd(loss, acc * inv_bhw);
+    if (lane == 0) atomicAdd(loss, acc * inv_bhw);
 }
 
 // EDM (training/loss.py:95-114): prep  x_n = x + sigma z, network input c_in x_n with c_in = 1 / sqrt(sigma^2 + sd^2)
@@ -1204,7 +1248,14 @@ static int modnorm_bwd_impl(const void* y, int64_t ldy, const float* g, void* dy
 extern "C" int swiftk_qknorm_bwd(const void* qkvh, const void* dqkvh, int64_t ld, const float* rn, void* dqkv, int64_t ldo,
                                  const float* scale, float* dscale, int64_t M, int heads, int head_dim, int dtype,
                                  void* stream) {
-    if (!qkvh || !dqkvh || !rn || !dqkv || !scale || !dscale || M <= 0) return SWIFTK_EINVAL;
+    if (!qkvh || !dqkvh || !rn || !dqkv || !scale || !dscale || M <= 0 || heads <= 0 || head_dim <= 0) return SWIFTK_EINVAL;
+    if (dtype != SWIFTK_BF16 && dtype != SWIFTK_F32) return SWIFTK_EINVAL;
+    // the kernel walks a head vector as <= 16 whole 16-byte chunks (one per lane of a 16-lane group) and keeps one LDS
+    // accumulator per head: anything else would be read and written in part only
+    const int esz = dtype == SWIFTK_BF16 ? 2 : 4, per = 16 / esz;
+    if (head_dim % per || head_dim / per > 16 || heads > 64) return SWIFTK_ESHAPE;
+    if (ld < (int64_t)3 * heads * head_dim || ldo < (int64_t)3 * heads * head_dim) return SWIFTK_ESHAPE;
+    if ((((uintptr_t)qkvh | (uintptr_t)dqkvh | (uintptr_t)dqkv) & 15) || (ld * esz) % 16 || (ldo * esz) % 16) return SWIFTK_EALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int inplace = (qkvh != dqkvh && dqkvh == dqkv) ? 1 : 0;  // the gradient buffer then has row stride ldo
     const int grid = grid_for(M * (inplace ? 2 : 3) * heads * 4);  // sixteen lanes per vector, four vectors per group and trip
