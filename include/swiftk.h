@@ -602,7 +602,7 @@ int swiftk_qkv_attention_fused(const void* x, int64_t ldx, const void* w, int64_
 
 typedef struct swiftk_layer {
     const void* qkv_w;   /* [3*heads*hd, kd] dtype                     (to_qkv.weight)            */
-    const void* wo_w;    /* [d, kd]          dtype                     (wo.weight)                */
+    const void* wo_w;    /* [d, kd]          dtype                     (wo.weight; swiftk_model.head_dim != 0: [d, k_pad(heads*hd)]) */
     const void* w1_w;    /* [2*mlp, kd]      dtype, rows interleaved gate_j, up_j (w1.weight)      */
     const void* w2_w;    /* [d, kmlp]        dtype                     (w2.weight)                */
     const float* scale;  /* [heads]                                    (Attention.scale)          */
@@ -656,6 +656,10 @@ typedef struct swiftk_model {
     const float* logvar_b;
     const void* head_w;            /* [round_up(out_ch*p1*p2, 4), kd] dtype (head.head.0.weight, zero rows appended) */
     const swiftk_layer* layers_host; /* HOST array of `depth` entries           */
+    int32_t head_dim;              /* 0 = dim / heads.  Otherwise the device-side head width hd (80 / 88 / 96) of a model whose own
+                                      width no kernel runs: each head's q, k and v carry zero lanes up to hd, so the attention inner
+                                      width heads * hd may exceed dim -- to_qkv is [3*heads*hd, kd] (head h at row 3*hd*h, zero rows
+                                      in the pad lanes) and wo [d, swiftk_gemm_k_pad(dtype, heads*hd)] (zero columns there) */
 } swiftk_model;
 
 /*

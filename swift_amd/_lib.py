@@ -75,6 +75,7 @@ class Model(C.Structure):
         + [(n, C.c_void_p) for n in ("pe_w", "pe_b", "pos", "freqs", "aux_w", "aux_b", "l1_w", "l1_b", "l2_w", "l2_b",
                                      "mod_w", "mod_b", "logvar_w", "logvar_b", "head_w")]
         + [("layers_host", C.POINTER(Layer))]
+        + [("head_dim", C.c_int32)]  # 0 = dim / heads, else the device-side head width (heads * head_dim may exceed dim)
     )
 
 

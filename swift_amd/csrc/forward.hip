@@ -3,6 +3,8 @@
 // Mirrors reference src/swift/models/swinv2.py:305-330 (+ precond.py:139-148, diffusion.py:459 folded in).
 #include "common.h"
 
+#include <algorithm>
+
 int g_fwd_tiled = 1;  // tuning key 5 (A/B only): 0 keeps q/k/v row-major between to_qkv and attention
 int g_x3_exact = 17;  // tuning key 11: the DEFAULT mask a host binding copies into swiftk_model.x3_exact when it packs the weights
                       // (the forward reads the model's own field, never this global: ADVICE r3)
@@ -37,7 +39,7 @@ inline int64_t al(int64_t v) { return (v + 255) & ~(int64_t)255; }
 bool model_ok(const swiftk_model* m) {
     if (!m || !m->layers_host) return false;
     if (m->dtype != SWIFTK_F32 && m->dtype != SWIFTK_BF16 && m->dtype != SWIFTK_BF16X3) return false;
-    if (m->depth <= 0 || m->dim <= 0 || m->heads <= 0 || m->dim % m->heads) return false;
+    if (m->depth <= 0 || m->dim <= 0 || m->heads <= 0 || m->head_dim < 0 || (m->head_dim == 0 && m->dim % m->heads)) return false;
     if (m->H % m->p1 || m->W % m->p2) return false;
     if (m->wh != 16 || m->ww != 16) return false;
     if ((m->H / m->p1) % 16 || (m->W / m->p2) % 16) return false;
@@ -72,9 +74,18 @@ inline bool tail_split_shape(const swiftk_model* m, int64_t M) {
     return tiles > g_persist_wgs && r > 0 && 2 * r <= g_persist_wgs;
 }
 
+// head width on the device and the attention inner width heads * hd: dim, unless swiftk_model.head_dim names a width whose heads carry
+// zero lanes (to_qkv's N and wo's K then exceed dim)
+inline int head_width(const swiftk_model* m) { return m->head_dim ? m->head_dim : m->dim / m->heads; }
+inline int64_t inner_width(const swiftk_model* m) { return (int64_t)m->heads * head_width(m); }
+inline int64_t att_ld(const swiftk_model* m) {  // row stride of the attention output = wo's operand
+    const int64_t inner = inner_width(m);
+    return inner == m->dim ? m->kd : swiftk_gemm_k_pad(m->dtype == SWIFTK_BF16 ? SWIFTK_BF16 : SWIFTK_F32, inner);
+}
+
 Layout make_layout(const swiftk_model* m, int B) {
     const int64_t es = m->dtype == SWIFTK_BF16 ? 2 : 4;
-    const int64_t ntok = (int64_t)(m->H / m->p1) * (m->W / m->p2), M = ntok * B, d = m->dim;
+    const int64_t ntok = (int64_t)(m->H / m->p1) * (m->W / m->p2), M = ntok * B, d = m->dim, inner = inner_width(m);
     Layout L;
     int64_t o = 0;
     L.emb = o; o += al(B * d * 4);
@@ -85,8 +96,8 @@ Layout make_layout(const swiftk_model* m, int B) {
     L.x = o; o += al(M * d * 4);
     L.xt = o; o += al(M * m->kd * es);
     L.xlo = o; o += m->dtype == SWIFTK_BF16 ? al(M * d * 2) : 0;  // low half of the pair-form residual stream
-    L.qkv = o; o += al(M * 3 * d * es);
-    L.att = o; o += al(M * m->kd * es);
+    L.qkv = o; o += al(M * 3 * inner * es);
+    L.att = o; o += al(M * att_ld(m) * es);
     L.y = o; o += al(M * d * es);
     L.yslab = o; o += small_m_splitk(m, M) ? al(2 * M * d * 4 + 8192) : tail_split_shape(m, M) ? al(2 * M * d * 2 + 8192) : 0;  // two fp32 slabs of the split-K wo / w2 (one unit per step)
     L.hmid = o; o += al(M * m->kmlp * es);
@@ -98,7 +109,7 @@ Layout make_layout(const swiftk_model* m, int B) {
     L.a3 = o;
     if (m->dtype == SWIFTK_BF16X3) {  // the split GEMM operand [M, k_pad(3 K)] bf16 of the widest GEMM input
         const int64_t kin = (int64_t)m->in_ch * m->p1 * m->p2;
-        const int64_t kmax = kin > m->mlp ? (kin > d ? kin : d) : (m->mlp > d ? m->mlp : d);
+        const int64_t kmax = std::max(std::max(kin, (int64_t)m->mlp), std::max(d, inner));
         o += al(M * swiftk_gemm_k_pad(SWIFTK_BF16, 3 * ((kmax + 3) & ~(int64_t)3)) * 2);
     }
     L.a3h = o;  // ... and the hidden activation's blocks, written by w1's epilogue while w1 still reads its own operand from a3
@@ -139,7 +150,10 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
     const int x3_exact = m->x3_exact;  // which GEMMs keep fp32 operands: fixed when the weights were packed
     const int dt = x3 ? SWIFTK_F32 : m->dtype;
     const int64_t es = dt == SWIFTK_BF16 ? 2 : 4;
-    const int gh = m->H / m->p1, gw = m->W / m->p2, d = m->dim, hd = m->dim / m->heads;
+    const int gh = m->H / m->p1, gw = m->W / m->p2, d = m->dim, hd = head_width(m);
+    // inner = heads * hd columns per q / k / v and per attention-output row (= d unless the heads carry zero lanes); katt = wo's row stride
+    const int64_t inner = inner_width(m), katt = att_ld(m);
+    const bool lanes = inner != d;
     const int64_t ntok = (int64_t)gh * gw, M = ntok * B;
     const int64_t ldmod = (int64_t)m->depth * 4 * d;
     float* emb = reinterpret_cast<float*>(ws + L.emb);
@@ -238,9 +252,9 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
         if (pair) RUN(swiftk_split_pair(x, d, xT, m->kd, xlo, d, lo_bits, M, d, stream));
         else RUN(swiftk_cast_pad(x, d, xT, m->kd, M, d, dt, stream));
     }
-    if (m->kd > d) {  // K-padding columns of the attention output must be finite (they meet zero weight columns)
-        hipLaunchKernelGGL(zero_cols_kernel, dim3(1024), dim3(256), 0, st, static_cast<char*>(att), m->kd * es, d * es,
-                           (m->kd - d) * es, M);
+    if (katt > inner) {  // K-padding columns of the attention output must be finite (they meet zero weight columns)
+        hipLaunchKernelGGL(zero_cols_kernel, dim3(1024), dim3(256), 0, st, static_cast<char*>(att), katt * es, inner * es,
+                           (katt - inner) * es, M);
         SWIFTK_CHECK_LAUNCH();
     }
     if (ff_split && ld3h > 3 * kvh) {  // k-padding behind the three blocks (the epilogue writes the blocks only)
@@ -257,6 +271,7 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
     // skips the padded half; otherwise it is the padded width itself
     const int64_t half_tile = (dt == SWIFTK_BF16 ? 64 : 32) / 2;
     const int64_t kdv = (m->kd - d == half_tile) ? d : m->kd;
+    const int64_t kav = (katt - inner == half_tile) ? inner : katt;  // ... and of wo, whose K is the attention inner width
     const bool do_shift = (m->sh != 0) || (m->sw != 0);
     // small batches, bf16 engine: wo / w2 and their ModulatedNorm as one complete-row kernel (gemm_rownorm.hip) -- 32-row
     // workgroups while those fill at most one round of the persistent grid's CUs, 64-row ones beyond
@@ -276,18 +291,18 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
         // bf16 operands, head_dim 80 / 88 / 96 (the 468 M variant, Swift-B, the 664 M variant): to_qkv, the cosine norm and the
         // window attention run as ONE kernel (q/k/v stay on the CU)
         if (dt == SWIFTK_BF16 && (hd == 80 || hd == 88 || hd == 96) && g_fwd_fused && m->wh == 16 && m->ww == 16) {
-            RUN(swiftk_qkv_attention_fused(xT, m->kd, ly.qkv_w, m->kd, ly.scale, att, m->kd, kdv, B, gh, gw, m->heads, hd,
+            RUN(swiftk_qkv_attention_fused(xT, m->kd, ly.qkv_w, m->kd, ly.scale, att, katt, kdv, B, gh, gw, m->heads, hd,
                                            shifted ? m->sh : 0, shifted ? m->sw : 0, stream));
         } else if (fuse_norm && dt == SWIFTK_BF16 && g_fwd_tiled) {
             // bf16: q/k/v leave the GEMM window-tiled, so every attention operand is one contiguous 44-KiB block
             RUN(swiftk_gemm_qkv_tiled(xT, m->kd, ly.qkv_w, m->kd, qkv, kdv, ly.scale, B, gh, gw, m->heads, hd,
                                       shifted ? m->sh : 0, shifted ? m->sw : 0, stream));
-            RUN(swiftk_window_attention(qkv, 3 * d, att, m->kd, ly.scale, B, gh, gw, m->heads, hd, shifted ? m->sh : 0,
+            RUN(swiftk_window_attention(qkv, 3 * inner, att, katt, ly.scale, B, gh, gw, m->heads, hd, shifted ? m->sh : 0,
                                         shifted ? m->sw : 0, dt, SWIFTK_ATTN_PRENORM | SWIFTK_ATTN_TILED, stream));
         } else {
             // (SWIFTK_BF16X3: the cosine logits multiply q-hat . k-hat by up to 100, so the split product's 4.5e-6 can reach the
             // softmax as 4.5e-4 -- x3_exact bit 0 keeps the whole GEMM on the exact-fp32 kernel, bit 6 only the hot head pairs)
-            RUN(G(xT, m->kd, ly.qkv_w, qkv, 3 * d, 3 * d, kdv, d, dt, fuse_norm ? SWIFTK_EPI_QKNORM : SWIFTK_EPI_NONE,
+            RUN(G(xT, m->kd, ly.qkv_w, qkv, 3 * inner, 3 * inner, kdv, d, dt, fuse_norm ? SWIFTK_EPI_QKNORM : SWIFTK_EPI_NONE,
                   fuse_norm ? ly.scale : nullptr, nullptr, fuse_norm ? hd : 0, (x3_exact & 1) != 0));
             // (bit 6 without bit 0 promises the hot-pair recompute: a model it cannot serve -- no fused norm, or hot pairs
             // without their fp32 weights -- is refused rather than run fully split)
@@ -308,7 +323,7 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
                     for (int h = 0; h < m->heads; ++h) {
                         if (!((hot_heads >> h) & 1)) continue;
                         const int64_t c0 = (int64_t)h * 3 * hd;
-                        RUN(swiftk_gemm(xT, m->kd, static_cast<const float*>(ly.qkv_w_f32) + c0 * m->kd, m->kd, static_cast<float*>(qkv) + c0, 3 * d, M,
+                        RUN(swiftk_gemm(xT, m->kd, static_cast<const float*>(ly.qkv_w_f32) + c0 * m->kd, m->kd, static_cast<float*>(qkv) + c0, 3 * inner, M,
                                         3 * hd, kdv, SWIFTK_F32, SWIFTK_F32, SWIFTK_EPI_QKNORM, ly.scale + h, nullptr, hd, stream));
                     }
                 } else
@@ -318,30 +333,31 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
                     // key 27 = 1: only q-hat and k-hat meet in the logits: the pair's two [q | k] column pairs (4 head_dim columns = ONE
                     // 352-wide tile column) are recomputed; v keeps its split product (pos_rows < 0 = the [q | k]-only form of QKNORM)
                     if (g_x3_qkonly == 1 &&
-                        swiftk_gemm(xT, m->kd, static_cast<const float*>(ly.qkv_w_f32) + c0 * m->kd, m->kd, static_cast<float*>(qkv) + c0, 3 * d, M,
+                        swiftk_gemm(xT, m->kd, static_cast<const float*>(ly.qkv_w_f32) + c0 * m->kd, m->kd, static_cast<float*>(qkv) + c0, 3 * inner, M,
                                     4 * hd, kdv, SWIFTK_F32, SWIFTK_F32, SWIFTK_EPI_QKNORM, ly.scale + 2 * pp, nullptr, -(int64_t)hd, stream) == 0)
                         continue;
                     RUN(swiftk_gemm(xT, m->kd, static_cast<const float*>(ly.qkv_w_f32) + c0 * m->kd, m->kd,
-                                    static_cast<float*>(qkv) + c0, 3 * d, M, 6 * hd, kdv, SWIFTK_F32, SWIFTK_F32, SWIFTK_EPI_QKNORM,
+                                    static_cast<float*>(qkv) + c0, 3 * inner, M, 6 * hd, kdv, SWIFTK_F32, SWIFTK_F32, SWIFTK_EPI_QKNORM,
                                     ly.scale + 2 * pp, nullptr, hd, stream));
                 }
             }
             // (round 6 also let the fp32 attention kernel write wo's [hi | lo | hi] operand blocks itself -- 8 B per element and a launch less:
             // 100.0 against 99.9 sample-steps/s, nothing; taken out again)
-            RUN(swiftk_window_attention(qkv, 3 * d, att, m->kd, ly.scale, B, gh, gw, m->heads, hd, shifted ? m->sh : 0,
+            RUN(swiftk_window_attention(qkv, 3 * inner, att, katt, ly.scale, B, gh, gw, m->heads, hd, shifted ? m->sh : 0,
                                         shifted ? m->sw : 0, dt, (fuse_norm ? SWIFTK_ATTN_PRENORM : 0) | (x3 && g_x3_attnpv ? SWIFTK_ATTN_PV_BF16X3 : 0),
                                         stream));
         }
-        if (rn_rows) {
+        // (the complete-row kernel, the tail split and the one-unit split-K take wo with K = dim: padded head lanes run the plain GEMM + norm)
+        if (rn_rows && !lanes) {
             RUN(swiftk_gemm_modnorm_residual_pair(att, m->kd, ly.wo_w, m->kd, kdv, xT, m->kd, xlo, d, ly.ln1_g, ly.ln1_b,
                                                   mod + (int64_t)(2 * i) * 2 * d, ldmod, M, d, ntok, 1e-6f, rn_rows, stream));
-        } else if (tail && (tail_rc = swiftk_gemm_tail_split_bf16(att, m->kd, ly.wo_w, m->kd, yslab, d, SS, M, d, kdv, tail3, stream)) != SWIFTK_ESHAPE) {
+        } else if (tail && !lanes && (tail_rc = swiftk_gemm_tail_split_bf16(att, m->kd, ly.wo_w, m->kd, yslab, d, SS, M, d, kdv, tail3, stream)) != SWIFTK_ESHAPE) {
             // (SWIFTK_ESHAPE: the GEMM takes no such walk right now -- ping-pong loop or persistent kernel switched off by a tuning key -- and has
             // launched nothing: the plain path below runs instead)
             RUN(tail_rc);
             RUN(swiftk_modnorm_residual_pair_halves_bf16(yslab, SS, tail3, xT, m->kd, xlo, ly.ln1_g, ly.ln1_b,
                                                          mod + (int64_t)(2 * i) * 2 * d, ldmod, M, d, ntok, 1e-6f, stream));
-        } else if (splitk && g_fwd_splitk >= 2) {
+        } else if (splitk && !lanes && g_fwd_splitk >= 2) {
             RUN(swiftk_gemm_splitk_bf16(att, m->kd, ly.wo_w, m->kd, yslab, d, SS, M, d, kdv, 2, stream));
             if (halves_norm)
                 RUN(swiftk_modnorm_residual_pair_halves_bf16(yslab, SS, nullptr, xT, m->kd, xlo, ly.ln1_g, ly.ln1_b,
@@ -349,12 +365,12 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
             else
             RUN(swiftk_modnorm_residual_pair_slabs_bf16(yslab, d, SS, xT, m->kd, xlo, d, lo_bits, ly.ln1_g, ly.ln1_b,
                                                         mod + (int64_t)(2 * i) * 2 * d, ldmod, M, d, ntok, 1e-6f, stream));
-        } else if (splitk) {
+        } else if (splitk && !lanes) {
             RUN(swiftk_gemm_splitk(att, m->kd, ly.wo_w, m->kd, yslab, d, M * d, M, d, kdv, SWIFTK_BF16, 2, stream));
             RUN(swiftk_modnorm_residual_pair_slabs(yslab, d, M * d, xT, m->kd, xlo, d, lo_bits, ly.ln1_g, ly.ln1_b,
                                                    mod + (int64_t)(2 * i) * 2 * d, ldmod, M, d, ntok, 1e-6f, stream));
         } else {
-            RUN(G(att, m->kd, ly.wo_w, y, d, d, kdv, d, dt, SWIFTK_EPI_NONE, nullptr, nullptr, 0, (x3_exact & 2) != 0));
+            RUN(G(att, katt, ly.wo_w, y, d, d, kav, inner, dt, SWIFTK_EPI_NONE, nullptr, nullptr, 0, (x3_exact & 2) != 0));
             if (pair)
                 RUN(swiftk_modnorm_residual_pair(y, d, xT, m->kd, xlo, d, lo_bits, ly.ln1_g, ly.ln1_b, mod + (int64_t)(2 * i) * 2 * d,
                                                  ldmod, M, d, ntok, 1e-6f, stream));

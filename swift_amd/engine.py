@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import types
 from typing import Optional, Sequence
 
 import torch
@@ -35,7 +36,63 @@ def check_head_dim(module, dtype) -> None:
     if heads <= 0 or d % heads or d // heads not in widths:
         raise SwiftkError(f"head_dim = dim / heads = {d} / {heads} = {d / max(heads, 1):g} is not supported by the gfx950 kernels: "
                           f"head_dim must be one of {', '.join(map(str, HEAD_DIMS))} (or 64 on the exact-fp32 attention); "
-                          f"choose model.heads so that dim / heads is one of them")
+                          f"choose model.heads so that dim / heads is one of them. SWIFTK_PAD_HEADS=1 runs a width of up to "
+                          f"{HEAD_DIMS[-1]} on zero-padded head lanes (forward and training engines)")
+
+
+def pad_heads_enabled() -> bool:
+    """The SWIFTK_PAD_HEADS switch, read when an engine is built (README, environment switches)."""
+    return os.environ.get("SWIFTK_PAD_HEADS", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+def head_lanes(dim: int, heads: int, dtype):
+    """(hd, hdp): the model's head width and the width its heads occupy on the device.  ``hdp == hd`` where a kernel runs the
+    width natively (``check_head_dim``); otherwise, with SWIFTK_PAD_HEADS set and 1 <= hd <= 96, the smallest of 80 / 88 / 96
+    that holds it -- each head's q, k and v then carry ``hdp - hd`` zero lanes (zero rows of to_qkv, zero columns of wo), which
+    leave the L2 norms, the cosine logits and the softmax as they are and come out of P V as zeros."""
+    dim, heads = int(dim), int(heads)
+    widths = HEAD_DIMS if dtype == torch.bfloat16 else HEAD_DIMS_F32
+    if heads > 0 and dim % heads == 0:
+        hd = dim // heads
+        if hd in widths:
+            return hd, hd
+        if pad_heads_enabled() and 1 <= hd <= HEAD_DIMS[-1]:
+            return hd, min(w for w in HEAD_DIMS if w >= hd)
+    check_head_dim(types.SimpleNamespace(dim=dim, heads=heads), dtype)
+    raise AssertionError("unreachable")  # pragma: no cover
+
+
+def pack_qkv_lanes(w: torch.Tensor, heads: int, hd: int, hdp: int) -> torch.Tensor:
+    """to_qkv.weight [heads * 3 * hd, d] -> [heads * 3 * hdp, d]: every q, k and v block of every head extended from ``hd`` to
+    ``hdp`` rows with zeros (head h then starts at row 3 * hdp * h).  Any device, any floating dtype."""
+    if hdp == hd:
+        return w
+    out = w.new_zeros(heads, 3, hdp, w.shape[1])
+    out[:, :, :hd] = w.reshape(heads, 3, hd, w.shape[1])
+    return out.reshape(heads * 3 * hdp, w.shape[1])
+
+
+def unpack_qkv_lanes(g: torch.Tensor, heads: int, hd: int, hdp: int) -> torch.Tensor:
+    """Adjoint of ``pack_qkv_lanes``: a lane-shaped gradient [heads * 3 * hdp, d] -> the parameter's [heads * 3 * hd, d]."""
+    if hdp == hd:
+        return g
+    return g.reshape(heads, 3, hdp, g.shape[1])[:, :, :hd].reshape(heads * 3 * hd, g.shape[1])
+
+
+def pack_wo_lanes(w: torch.Tensor, heads: int, hd: int, hdp: int) -> torch.Tensor:
+    """wo.weight [d, heads * hd] -> [d, heads * hdp]: zero columns where the attention output carries its pad lanes."""
+    if hdp == hd:
+        return w
+    out = w.new_zeros(w.shape[0], heads, hdp)
+    out[:, :, :hd] = w.reshape(w.shape[0], heads, hd)
+    return out.reshape(w.shape[0], heads * hdp)
+
+
+def unpack_wo_lanes(g: torch.Tensor, heads: int, hd: int, hdp: int) -> torch.Tensor:
+    """Adjoint of ``pack_wo_lanes``: [d, heads * hdp] -> [d, heads * hd]."""
+    if hdp == hd:
+        return g
+    return g.reshape(g.shape[0], heads, hdp)[:, :, :hd].reshape(g.shape[0], heads * hd)
 
 
 class SwinEngine:
@@ -56,7 +113,7 @@ class SwinEngine:
         return tuple((p.data_ptr(), p._version) for p in self.module.parameters())
 
     def check_shape(self) -> None:
-        check_head_dim(self.module, self.dtype)
+        self.hd, self.hdp = head_lanes(self.module.dim, self.module.heads, self.dtype)
 
     def refresh(self) -> None:
         stamp = self._param_stamp()
@@ -78,7 +135,7 @@ class SwinEngine:
         exact_mask = int(os.environ.get("SWIFTK_X3_EXACT", "80"))  # travels in the model descriptor (mo.x3_exact), per engine
         tau_max = float(os.environ.get("SWIFTK_X3_TAU", "25"))
         adaptive = (x3 and bool(exact_mask & 64) and not (exact_mask & 1) and m.heads % 2 == 0
-                    and (m.dim // m.heads) in (80, 88, 96))
+                    and self.hdp in (80, 88, 96))
         if x3 and (exact_mask & 64) and not adaptive:
             # the hot-pair recompute exists for head_dim 80 / 88 / 96 and an even head count only: any other shape keeps to_qkv on the exact
             # kernel (bit 0, the round-3 default) instead of running it fully split with no recompute (2.8e-4 on Swift-B)
@@ -92,6 +149,10 @@ class SwinEngine:
         # extra SwiGLU columns are silu(0) * 0 = 0 and land in w2's zero K padding
         mlp_e = (mlp + 7) // 8 * 8
         kd, kmlp, kpe = ops.k_pad(dt, d), ops.k_pad(dt, mlp_e), ops.k_pad(dt, m.in_channels * p1 * p2)
+        # SWIFTK_PAD_HEADS: a head width no kernel runs (66, or 64 / 32 on bf16) occupies hdp = 80 / 88 / 96 lanes, the extra ones
+        # zero -- to_qkv gains zero rows, wo zero columns, and the attention inner width heads * hdp exceeds dim
+        hd, hdp = self.hd, self.hdp
+        katt = kd if hdp == hd else ops.k_pad(dt, heads * hdp)
         keep = []
 
         def f32(t):
@@ -114,7 +175,8 @@ class SwinEngine:
             w1i = w1.view(2, mlp, d).permute(1, 0, 2).reshape(2 * mlp, d)  # rows: gate_0, up_0, gate_1, up_1, ...
             if mlp_e != mlp:
                 w1i = torch.cat([w1i, w1i.new_zeros(2 * (mlp_e - mlp), d)], 0)
-            layers[i].qkv_w = gemm_w(att.to_qkv.weight, kd, exact=bool(exact_mask & 1))
+            qkv_w = pack_qkv_lanes(att.to_qkv.weight.detach(), heads, hd, hdp)
+            layers[i].qkv_w = gemm_w(qkv_w, kd, exact=bool(exact_mask & 1))
             if adaptive:
                 tau = torch.exp(torch.clamp(att.scale.detach().reshape(-1).float(), max=math.log(100.0))).cpu()
                 hot = 0
@@ -128,8 +190,8 @@ class SwinEngine:
                     if hot & (1 << 31):
                         hot -= 1 << 32  # (the field is a signed 32-bit integer)
                 layers[i].qk_exact_pairs = hot
-                layers[i].qkv_w_f32 = gemm_w(att.to_qkv.weight, kd, exact=True) if hot & 0xffff else None
-            layers[i].wo_w = gemm_w(att.wo.weight, kd, exact=bool(exact_mask & 2))
+                layers[i].qkv_w_f32 = gemm_w(qkv_w, kd, exact=True) if hot & 0xffff else None
+            layers[i].wo_w = gemm_w(pack_wo_lanes(att.wo.weight.detach(), heads, hd, hdp), katt, exact=bool(exact_mask & 2))
             layers[i].w1_w = gemm_w(w1i, kd, exact=bool(exact_mask & 4))
             layers[i].w2_w = gemm_w(ff.w2.weight, kmlp, exact=bool(exact_mask & 8))
             layers[i].scale = f32(att.scale.reshape(-1))
@@ -170,6 +232,7 @@ class SwinEngine:
             hw = torch.cat([hw, hw.new_zeros(4 - hw.shape[0] % 4, hw.shape[1])], 0)
         mo.head_w = gemm_w(hw, kd, exact=bool(exact_mask & 32))
         mo.layers_host = C.cast(layers, C.POINTER(Layer))
+        mo.head_dim = 0 if hdp == hd else hdp  # (0 = dim / heads: a native width's descriptor is what it always was)
         keep.append(layers)
         self.model, self._keep, self._stamp = mo, keep, stamp
 

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from ._lib import (ATTN_PRENORM, BF16, EPI_ACCUM, EPI_BIAS_POS, EPI_NONE, EPI_QKNORM, EPI_SWIGLU_BOTH, EPI_SWIGLU_BWD, F32, SwiftkError, check, lib)
-from .engine import check_head_dim
+from .engine import head_lanes, pack_qkv_lanes, pack_wo_lanes, unpack_qkv_lanes, unpack_wo_lanes
 from .graphs import GraphCache
 
 _BF = torch.bfloat16
@@ -72,8 +72,10 @@ def _padded(rows, width, valid):
 class SwinTrainEngine:
     def __init__(self, module):
         self.m = module
-        check_head_dim(module, torch.bfloat16)  # (names head_dim and the widths the kernels run)
-        self.hd = module.dim // module.heads
+        # hd0: the model's head width; hd: the width its heads occupy on the device (SWIFTK_PAD_HEADS: zero lanes up to 80 / 88 / 96,
+        # engine.head_lanes -- which names head_dim and the widths the kernels run when it refuses)
+        self.hd0, self.hd = head_lanes(module.dim, module.heads, torch.bfloat16)
+        self.inner = module.heads * self.hd  # columns per q / k / v and per attention-output row (= dim unless lanes are padded)
         if self.hd not in (80, 88, 96) or module.heads % 2:
             raise SwiftkError("the training kernels are built for head_dim 80 / 88 / 96 and an even head count")
         self._stamp = None
@@ -101,7 +103,9 @@ class SwinTrainEngine:
         mlp_e = self.mlp_e = (mlp + 7) // 8 * 8
         self.kd, self.kmlp = ops.k_pad(_BF, d), ops.k_pad(_BF, mlp_e)
         self.kpe = ops.k_pad(_BF, m.in_channels * m.patch_size[0] * m.patch_size[1])
-        self.kqkv = ops.k_pad(_BF, 3 * d)
+        heads, hd0, hd, inner = m.heads, self.hd0, self.hd, self.inner
+        self.katt = ops.k_pad(_BF, inner)
+        self.kqkv = ops.k_pad(_BF, 3 * inner)
         self.kh = ops.k_pad(_BF, 2 * mlp_e)
         po = m.out_channels * m.patch_size[0] * m.patch_size[1]
         self.kpo = ops.k_pad(_BF, po)
@@ -137,8 +141,9 @@ class SwinTrainEngine:
 
         self.L = []
         for att, ff in m.transformer.layers:
-            qkv, qkv_t = both(att.to_qkv.weight, self.kd, self.kqkv)
-            wo, wo_t = both(att.wo.weight, self.kd, self.kd)
+            # (padded head lanes: zero rows of to_qkv / zero columns of wo on the host side, then one pass each, as the MLP width below)
+            qkv, qkv_t = both(pack_qkv_lanes(att.to_qkv.weight.detach(), heads, hd0, hd), self.kd, self.kqkv)
+            wo, wo_t = both(pack_wo_lanes(att.wo.weight.detach(), heads, hd0, hd), self.katt, self.kd)
             if mlp_e != mlp:  # (the padded MLP width of dim 1280: interleave and zero-extend on the host side, then one pass each)
                 w1i = ff.w1.weight.detach().view(2, mlp, d).permute(1, 0, 2).reshape(2 * mlp, d)
                 w1i = torch.cat([w1i, w1i.new_zeros(2 * (mlp_e - mlp), d)], 0)
@@ -223,7 +228,7 @@ class SwinTrainEngine:
         self.refresh()
         m = self.m
         M = B * m.grid_size[0] * m.grid_size[1]
-        per_token_layer = 2 * (3 * self.kd + 3 * m.dim + 2 * m.dim + 2 * self.mlp_e + self.kmlp) + 4 * 3 * m.heads
+        per_token_layer = 2 * (2 * self.kd + self.katt + 3 * self.inner + 2 * m.dim + 2 * self.mlp_e + self.kmlp) + 4 * 3 * m.heads
         return M * m.depth * per_token_layer
 
     # ------------------------------------------------------------------ forward (saves activations)
@@ -247,7 +252,7 @@ class SwinTrainEngine:
         m = self.m
         dev = srcs[0].device
         B = srcs[0].shape[0]
-        d, heads, mlp = m.dim, m.heads, self.mlp_e
+        d, heads, mlp, inner = m.dim, m.heads, self.mlp_e, self.inner
         gh, gw = m.grid_size
         ntok = gh * gw
         M = B * ntok
@@ -301,14 +306,14 @@ class SwinTrainEngine:
         for i, (att, ff) in enumerate(m.transformer.layers):
             W = self.L[i]
             sh = tuple(m.shift_size) if (do_shift and i % 2) else (0, 0)
-            qkvh = torch.empty(M, 3 * d, dtype=_BF, device=dev)
+            qkvh = torch.empty(M, 3 * inner, dtype=_BF, device=dev)
             rn = torch.empty(M, 3 * heads, dtype=torch.float32, device=dev)
             _gemm(xT, W["qkv"], qkvh, EPI_QKNORM, W["scale"], rn, pos_rows=self.hd, k=d)  # (QKNORM: head_dim rides in pos_rows)
-            a = _padded(M, self.kd, d)
-            ops.window_attention(qkvh.view(B, ntok, 3 * d), None, (gh, gw), heads, sh, out=a.view(B, ntok, self.kd),
+            a = _padded(M, self.katt, inner)
+            ops.window_attention(qkvh.view(B, ntok, 3 * inner), None, (gh, gw), heads, sh, out=a.view(B, ntok, self.katt),
                                  flags=ATTN_PRENORM)
             y1 = torch.empty(M, d, dtype=_BF, device=dev)
-            _gemm(a, W["wo"], y1, k=d)
+            _gemm(a, W["wo"], y1, k=inner)
             msl1 = mod[:, (2 * i) * 2 * d:(2 * i + 1) * 2 * d]
             xT_mid = norm_res(y1, att.norm.norm.weight.detach().float(), att.norm.norm.bias.detach().float(), msl1, xT)
             h = torch.empty(M, 2 * mlp, dtype=_BF, device=dev)
@@ -364,6 +369,7 @@ class SwinTrainEngine:
         dev = dout.device
         B, M = ctx["B"], ctx["M"]
         d, heads, mlp, mlp0 = m.dim, m.heads, self.mlp_e, m.mlp_dim
+        hd0, hd, inner = self.hd0, self.hd, self.inner
         gh, gw = m.grid_size
         ntok = gh * gw
         L = lib()
@@ -395,9 +401,12 @@ class SwinTrainEngine:
         # instead of once per layer; every kernel writes the valid columns only)
         dy2, dy1 = _padded(M, self.kd, d), _padded(M, self.kd, d)
         dh = _padded(M, max(self.kh, 2 * mlp), 2 * mlp)
-        dqkv = _padded(M, self.kqkv, 3 * d)
-        datt = torch.empty(M, self.kd, dtype=_BF, device=dev)
+        dqkv = _padded(M, self.kqkv, 3 * inner)
+        datt = torch.empty(M, self.katt, dtype=_BF, device=dev)
         g1i = torch.empty(2 * mlp, d, dtype=torch.float32, device=dev)
+        if hd != hd0:  # lane-shaped weight gradients of wo / to_qkv; their pad columns / rows are dropped on the way into .grad
+            gwo = torch.empty(d, inner, dtype=torch.float32, device=dev)
+            gqkv = torch.empty(3 * inner, d, dtype=torch.float32, device=dev)
         for i in reversed(range(m.depth)):
             att, ff = m.transformer.layers[i]
             W, A = self.L[i], ctx["layers"][i]
@@ -424,20 +433,28 @@ class SwinTrainEngine:
             # ---- attention branch
             self._modnorm_bwd(A["y1"], dx, dy1, att.norm.norm, mod[:, (2 * i) * 2 * d:(2 * i + 1) * 2 * d],
                               dmod[:, (2 * i) * 2 * d:(2 * i + 1) * 2 * d], M, d, ntok)
-            _gemm(dy1, W["wo_t"], datt, k=d)  # N = d columns written, row stride kd
-            self._wgrad(dy1, A["att"], d, d, G(att.wo.weight))
+            _gemm(dy1, W["wo_t"], datt, k=d)  # N = inner columns written, row stride katt
+            if hd == hd0:
+                self._wgrad(dy1, A["att"], d, d, G(att.wo.weight))
+            else:
+                self._wgrad(dy1, A["att"], d, inner, gwo, accumulate=False)
+                G(att.wo.weight).add_(unpack_wo_lanes(gwo, heads, hd0, hd))
             # d(q | k | v) lands in the to_qkv data-gradient GEMM's operand buffer (row stride kqkv): the attention backward applies
             # the QK-norm backward to its accumulators on their way out (head_dim 88; elsewhere a second pass rewrites the q-hat / k-hat
             # vectors in place -- v's gradient is already final)
             sh = A["shift"]
             gscale = G(att.scale)  # [heads, 1, 1] fp32, contiguous: the kernel accumulates (atomicAdd) straight into it
             assert gscale.is_contiguous() and gscale.numel() == heads
-            check(L.swiftk_window_attention_bwd_qknorm(A["qkvh"].data_ptr(), 3 * d, A["att"].data_ptr(), datt.data_ptr(), self.kd,
+            check(L.swiftk_window_attention_bwd_qknorm(A["qkvh"].data_ptr(), 3 * inner, A["att"].data_ptr(), datt.data_ptr(), self.katt,
                                                        dqkv.data_ptr(), self.kqkv, W["scale"].data_ptr(), A["rn"].data_ptr(),
                                                        gscale.data_ptr(), B, gh, gw, heads, self.hd, sh[0], sh[1], BF16, _s()),
                   "swiftk_window_attention_bwd_qknorm")
-            _gemm(dqkv, W["qkv_t"], dx, EPI_ACCUM, k=3 * d)
-            self._wgrad(dqkv, A["xT_in"], 3 * d, d, G(att.to_qkv.weight))
+            _gemm(dqkv, W["qkv_t"], dx, EPI_ACCUM, k=3 * inner)
+            if hd == hd0:
+                self._wgrad(dqkv, A["xT_in"], 3 * d, d, G(att.to_qkv.weight))
+            else:
+                self._wgrad(dqkv, A["xT_in"], 3 * inner, d, gqkv, accumulate=False)
+                G(att.to_qkv.weight).add_(unpack_qkv_lanes(gqkv, heads, hd0, hd))
             if grads_final is not None:  # everything of layer i except its modulation Linears (those follow in _embed_bwd)
                 grads_final([p for n, p in m.transformer.layers[i].named_parameters() if "modulation" not in n])
         # ---- patch embedding: x0 = ape @ Wpe^T + b + pos

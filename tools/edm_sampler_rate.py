@@ -3,7 +3,10 @@
 evaluations per sample-step for both.  The two solvers alternate in one process, timed with device events after a warm-up,
 at 1 and 8 units per batch, for the bf16 and the bf16x3 engines.  Prints one JSON line per cell and a summary line.
 
-    python tools/edm_sampler_rate.py [--reps 3] [--units 1,8] [--dtypes bf16,bf16x3]
+    python tools/edm_sampler_rate.py [--reps 3] [--units 1,8] [--dtypes bf16,bf16x3] [--heads 12]
+
+``--heads 16`` is the reference's EDM model (16 heads of 66): it needs SWIFTK_PAD_HEADS=1 in the environment and runs each head
+on 80 lanes; its rate against ``--heads 12`` at the same depth and units is what the padded lanes cost.
 """
 import argparse
 import json
@@ -21,11 +24,12 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--units", default="1,8")
 ap.add_argument("--dtypes", default="bf16,bf16x3")
 ap.add_argument("--num-steps", type=int, default=20)
+ap.add_argument("--heads", type=int, default=12)
 a = ap.parse_args()
 
 NV, NF, IMG = 69, 3, [128, 256]
 mcfg = dict(_target_="swift.models.swinv2.SwinV2", window_size=[16, 16], shift_size=[8, 8], patch_size=[2, 2], depth=12,
-            dim=1056, heads=12)
+            dim=1056, heads=a.heads)
 torch.manual_seed(0)
 edm = EDMPrecond(mcfg, IMG, NV, NV + NF, auxiliary_dim=1)
 for p in edm.parameters():  # (the zero-initialised head would make F = 0: give every weight a value)
@@ -59,7 +63,7 @@ for dname in a.dtypes.split(","):
                 e1.synchronize()
                 ms[k].append(e0.elapsed_time(e1))
         rate = {k: B * 1000.0 / sorted(v)[len(v) // 2] for k, v in ms.items()}
-        row = dict(dtype=dname, units=B, num_steps=N, evaluations=2 * N - 1, edm_rate=round(rate["edm"], 3),
+        row = dict(dtype=dname, heads=a.heads, units=B, num_steps=N, evaluations=2 * N - 1, edm_rate=round(rate["edm"], 3),
                    dpm2s_rate=round(rate["2s"], 3), ratio=round(rate["edm"] / rate["2s"], 4), unit="sample-steps/s")
         rows.append(row)
         print(json.dumps(row), flush=True)
