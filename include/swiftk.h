@@ -342,6 +342,10 @@ int swiftk_profile_gemm(int epilogue, int64_t N);
  * key 28 = split engine: the fp32 attention kernel's P V as three bf16 products (1; 0 = exact fp32 like its q k^T),
  * key 29 = small batches of the bf16 engine (default 3): bit 0 = wo / w2 through swiftk_gemm_tail_split_bf16 where the persistent
  *          walk's last round is at most half full, bit 1 = swiftk_modnorm_residual_pair_halves_bf16 behind the one-unit split-K,
+ * key 30 = swiftk_qkv_attention_fused outside its MFMA loops (default 3): bit 0 = straight-line k-loop -> core hand-off (column half,
+ *          block classes and store offsets resolved at compile time: no per-store exec region), bit 1 = straight-line output stage
+ *          (scale + pack once per item, one exec region per 16-row round, 32-bit store offsets) and incremental item decode;
+ *          0 = the round-3..6 forms.  Bit-equal results at every value (tools/qkv_handoff_probe.py times the four),
  * key 25 = clears through hipMemsetAsync instead of a kernel (0; diagnosis only; bit 1 = the library's internal clears --
  * swiftk_modnorm_bwd's workspace, swiftk_scm_target's scratch --, bit 2 = swiftk_zero_f32, bit 4 = a check kernel behind
  * swiftk_modnorm_bwd's clear records what it left non-zero: swiftk_zero_check_report). */
@@ -590,7 +594,9 @@ int swiftk_cast_pad_t(const float* W, int64_t ldw, int64_t rows, int64_t cols, v
  *   x    [B*gh*gw, ldx] bf16 token-major (K valid columns; K = 16.5 k-tiles style padding as in swiftk_gemm)
  *   w    [3*heads*head_dim, ldw] bf16 (to_qkv.weight as stored: per-head [q|k|v] rows)
  *   out  [B*gh*gw, ldo] bf16, head h in columns [head_dim h, head_dim (h + 1)), token order (un-rolled)
- * SWIFTK_ESHAPE for any other head_dim, a grid that is not a multiple of the window, a shift outside the grid.
+ * SWIFTK_ESHAPE for any other head_dim, a grid that is not a multiple of the window, a shift outside the grid, and for a sample
+ * whose operand or output rows span 4 GiB or more (gh * gw * ldx * 2 or gh * gw * ldo * 2 >= 2^32: the kernel addresses
+ * both with 32-bit byte offsets from a per-sample base); nothing is launched then.
  */
 int swiftk_qkv_attention_fused(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* scale, void* out,
                                int64_t ldo, int64_t K, int B, int gh, int gw, int heads, int head_dim, int shift_h,

@@ -29,6 +29,7 @@
 
 int g_attn_dbg = 0;
 int g_attn_pp = 1;  // tuning key 21 (qkv_attn.hip): ping-pong k-loop of the fused to_qkv + attention kernel
+int g_attn_sl = 3;  // tuning key 30 (qkv_attn.hip): bit 0 straight-line hand-off, bit 1 straight-line output stage + item decode
 
 namespace {
 

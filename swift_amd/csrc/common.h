@@ -214,4 +214,5 @@ extern int g_fwd_rownorm;  // tuning key 23: wo / w2 + norm as one complete-row 
 extern int g_rownorm_dbg;
 extern int g_tn_pp;  // tuning key 22: ping-pong k-loop of gemm_tn_kernel
 extern int g_attn_pp;  // tuning key 21: ping-pong k-loop of the fused to_qkv + attention kernel
+extern int g_attn_sl;  // tuning key 30: straight-line hand-off (bit 0) / output stage and item decode (bit 1) of that kernel
 extern int g_attn_dbg;  // tuning key 4: attention ablation bits (timing experiments only)

@@ -1728,6 +1728,7 @@ extern "C" int swiftk_set_tuning(int key, int value) {
         case 27: g_x3_qkonly = value; return 0;
         case 28: g_x3_attnpv = value; return 0;
         case 29: g_fwd_tail = value; return 0;
+        case 30: g_attn_sl = value & 3; return 0;
         case 25:
             g_zero_memset = value;
             return (value & 4) ? swiftk_zero_check_enable() : 0;
@@ -1765,6 +1766,7 @@ extern "C" int swiftk_get_tuning(int key) {
         case 27: return g_x3_qkonly;
         case 28: return g_x3_attnpv;
         case 29: return g_fwd_tail;
+        case 30: return g_attn_sl;
     }
     return SWIFTK_EINVAL;
 }

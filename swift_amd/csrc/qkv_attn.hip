@@ -99,6 +99,7 @@ struct FusedArgs {
     int B, gh, gw, heads, sh, sw;
     int nk, khalf;      // k-tiles, and whether the last one is half full
     int dbg;            // timing experiments: 1 = skip the attention core, 2 = every item reads head 0's weights, 4 = no parking writes, 8 = no norm + no parking writes
+                        // (4 and 8 were written for the run-time hand-off, SL bit 0 clear; the straight-line form skips norm and writes for either)
 };
 
 __device__ __forceinline__ int win_token(int wy, int wx, int j, int gh, int gw, int sh, int sw) {
@@ -109,12 +110,22 @@ __device__ __forceinline__ int win_token(int wy, int wx, int j, int gh, int gw, 
     return gy * gw + gx;
 }
 
+// What gemm_part is instantiated for: the wave's column blocks, and the column half itself where the hand-off is the
+// straight-line form (WN 0 / 1; the block count does not name the half at head_dim 96, 9 | 9).  WN = -1: the half is a run-time
+// value, as in the round-3..6 hand-off.
+template <int NI_, int WN_>
+struct PartTag {
+    static constexpr int NI = NI_, WN = WN_;
+};
+
 template <int N>
 __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int HD, bool PP>
+// SL (tuning key 30): bit 0 = straight-line k-loop -> core hand-off, bit 1 = straight-line output stage + incremental item
+// decode; 0 = the round-3..6 forms, kept as the yardstick for bit-equality and timing (as PP = false is for the k-loop).
+template <int HD, bool PP, int SL>
 __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
     using G = Geo<HD>;
     constexpr int NI0 = G::NI0, NI1 = G::NI1, WT0 = G::WT0, NV0 = G::NV0, NV1 = G::NV1, BNP = G::BNP, STAGE = G::STAGE, ROW = G::ROW;
@@ -261,6 +272,10 @@ __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
 
     int b, w, h;
     decode(first, b, w, h);
+    // (SL bit 1) the walk's step as (samples, windows, heads), decomposed once: an item's successor is three adds and two
+    // carries on the scalar unit instead of two divisions by run-time values
+    int st_b = 0, st_w = 0, st_h = 0;
+    if constexpr (SL & 2) decode(istep, st_b, st_w, st_h);
     set_item(b, w, h);
     issue_all(lds0 + OFF_S0, 0u, false);
     bool have_prev = false;
@@ -268,11 +283,21 @@ __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
     for (int item = first; item < last; item += istep) {
         int nb = b, nwn = w, nh = h;
         const bool has_next = item + istep < last;
-        if (has_next) decode(item + istep, nb, nwn, nh);
+        if (has_next) {
+            if constexpr (SL & 2) {
+                nh = h + st_h;
+                nwn = w + st_w;
+                nb = b + st_b;
+                if (nh >= a.heads) { nh -= a.heads; ++nwn; }
+                if (nwn >= nw) { nwn -= nw; ++nb; }
+            } else {
+                decode(item + istep, nb, nwn, nh);
+            }
+        }
 
         // =========================================================== k-loop: acc[i][j] = X_window W_head^T (fp32)
-        auto gemm_part = [&](auto ni_tag) {
-        constexpr int NI = decltype(ni_tag)::value;
+        auto gemm_part = [&](auto part_tag) {
+        constexpr int NI = decltype(part_tag)::NI, WN = decltype(part_tag)::WN;
         f32x4 acc[MI][NI];
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -414,6 +439,61 @@ __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
 
         // =========================================================== epilogue: cosine norm on the accumulators -> LDS
         __builtin_amdgcn_s_barrier();  // every wave is done reading the last stage: both stages may be overwritten
+        if constexpr (WN >= 0) {
+            // Straight-line form (SL bit 0).  The lane id stays opaque (see below), but what is derived from it is masked, so r16 < 16
+            // and g4 < 4 are known and every column test folds: a 16-column block is all q/k, all v, the one q|v block (head_dim 88,
+            // block 5: lanes g4 < 2 hold q/k columns 80..87, the others v) or the v|pad block (head_dim 88, half 1, block 8).  The
+            // column half is a template parameter, so nv, v0, the destination tile and whether tau applies are constants; a store's
+            // address is one base VGPR per tile plus an immediate (row group 16 i rows, block 32 j bytes).  The q|v block takes ONE
+            // store, address and factor (f or 1.0f: exact, v's bits do not change) selected per lane; the pad lanes are masked once
+            // per wave behind the row groups.  Same values, same order of additions as the run-time form below: bit-equal outputs.
+            int el = lane;
+            asm volatile("" : "+v"(el));
+            const int r16 = el & 15, g4 = (el >> 4) & 3;
+            constexpr int NV = WN ? NV1 : NV0, V0 = WN ? NV0 : 0;
+            constexpr int NQ = HD / 16, MIXG = (HD % 16) / 4;                 // whole q/k blocks; q/k lane groups of the q|v block
+            constexpr int NVE = (HD + NV) / 16, PADG = ((HD + NV) % 16) / 4;  // end of the whole v blocks; v lane groups of the v|pad block
+            constexpr int JV = NQ + (MIXG > 0);                               // first whole v block
+            static_assert(HD % 4 == 0 && NVE + (PADG > 0) == NI && JV <= NVE, "column blocks of a half");
+            if (!(a.dbg & 12)) {  // (timing probes 4 / 8, WRONG results: this form skips the whole hand-off for either)
+                float tau = 1.0f;
+                if constexpr (WN == 0) tau = __expf(fminf(a.scale[h], 4.605170185988092f));
+                char* qkb = smem + (WN ? OFF_K : OFF_Q) + (wm * 64 + r16) * ROW + g4 * 8;
+                char* vvb = smem + OFF_V + (wm * 64 + r16) * VROW + g4 * 8 + (V0 - HD) * 2;  // + 32 j: v column 16 j + 4 g4 - HD + V0
+                const bool mix_q = g4 < MIXG;
+                auto park = [](char* p, const f32x4 v, const float s) {
+                    *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16(v[0] * s, v[1] * s), pack_bf16(v[2] * s, v[3] * s));
+                };
+                auto park_v = [](char* p, const f32x4 v) {
+                    *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
+                };
+                auto sq = [](const f32x4 v) { return (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]); };
+#pragma unroll
+                for (int i = 0; i < MI; ++i) {
+                    float ss = 0.f;
+#pragma unroll
+                    for (int j = 0; j < NQ; ++j) ss += sq(acc[i][j]);
+                    if constexpr (MIXG > 0) {
+                        const float t = sq(acc[i][NQ]);
+                        ss += mix_q ? t : 0.f;
+                    }
+                    ss += __shfl_xor(ss, 16, 64);
+                    ss += __shfl_xor(ss, 32, 64);
+                    const float f = tau / fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+                    for (int j = 0; j < NQ; ++j) park(qkb + i * 16 * ROW + 32 * j, acc[i][j], f);
+                    if constexpr (MIXG > 0) park(mix_q ? qkb + i * 16 * ROW + 32 * NQ : vvb + i * 16 * VROW + 32 * NQ, acc[i][NQ], mix_q ? f : 1.0f);
+#pragma unroll
+                    for (int j = JV; j < NVE; ++j) park_v(vvb + i * 16 * VROW + 32 * j, acc[i][j]);
+                }
+                if constexpr (PADG > 0) {
+                    if (g4 < PADG) {
+#pragma unroll
+                        for (int i = 0; i < MI; ++i) park_v(vvb + i * 16 * VROW + 32 * NVE, acc[i][NVE]);
+                    }
+                }
+            }
+        } else {
         // Everything lane-derived below is rebuilt from an opaque copy of the lane id: left visible, hipcc hoists the
         // epilogue's, the attention core's and the output stage's address registers above the k-loop and spills inside it.
         int el = lane;
@@ -459,8 +539,13 @@ __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
                 }
             }
         }
+        }
         };
-        if (wn == 0) gemm_part(std::integral_constant<int, NI0>{}); else gemm_part(std::integral_constant<int, NI1>{});
+        if constexpr (SL & 1) {
+            if (wn == 0) gemm_part(PartTag<NI0, 0>{}); else gemm_part(PartTag<NI1, 1>{});
+        } else {
+            if (wn == 0) gemm_part(PartTag<NI0, -1>{}); else gemm_part(PartTag<NI1, -1>{});
+        }
         int el = lane;
         asm volatile("" : "+v"(el));
         const int c32 = el & 31, hh = el >> 5;
@@ -608,7 +693,58 @@ __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
                 for (int p = 0; p < 4; ++p) issue_piece(lds0 + OFF_S0, 0u, p);
             }
         }
-        {
+        if constexpr (SL & 2) {
+            // Straight-line form (SL bit 1): the lane's fields are masked (hh < 2: `d < HD` folds; l6 < 64: only the last chunk
+            // round is partial), the 48 scalings and 24 packs run once on all 64 lanes instead of under each round's half mask,
+            // a round's 16 rows are ONE window row (wave-uniform gy, added to the scalar base), and a lane's grid column and
+            // 16-B chunk -- the same in both rounds -- give a 32-bit byte offset computed once per item (the entry point
+            // refuses an output of 4 GiB or more per sample).  A slab's rows are contiguous, so chunk c lies at 16 c.
+            constexpr int NCH = (OROWS * CPR + 63) / 64;
+            const int l6 = el & 63, c32o = el & 31, hho = (el >> 5) & 1;
+            uint2 pk[DB][4];
+#pragma unroll
+            for (int db = 0; db < DB; ++db)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    if (db * 32 + g * 8 < HD)  // (d = 32 db + 8 g + 4 hh .. + 3: HD is a multiple of 8)
+                        pk[db][g] = make_uint2(pack_bf16(o[db][4 * g] * rl, o[db][4 * g + 1] * rl),
+                                               pack_bf16(o[db][4 * g + 2] * rl, o[db][4 * g + 3] * rl));
+            const int wy = w / nwx, wx = w - wy * nwx;
+            const uint32_t ldo_b = (uint32_t)a.ldo * 2u;
+            char* obase = reinterpret_cast<char*>(a.out) + ((int64_t)b * ntok * a.ldo + h * HD) * 2;
+            uint32_t coff[NCH];
+#pragma unroll
+            for (int t = 0; t < NCH; ++t) {
+                const int c = l6 + 64 * t, row = c / CPR, cc = c - row * CPR;
+                int gx = wx * 16 + row + a.sw;
+                gx = gx >= a.gw ? gx - a.gw : gx;
+                coff[t] = (uint32_t)gx * ldo_b + (uint32_t)cc * 16u;
+            }
+            char* wslab = oslab + (c32o & (OROWS - 1)) * ROW + hho * 8;
+            const char* rslab = oslab + l6 * 16;
+#pragma unroll
+            for (int rnd = 0; rnd < ORND; ++rnd) {
+                int gy = wy * 16 + wv * 2 + rnd + a.sh;
+                gy = gy >= a.gh ? gy - a.gh : gy;
+                char* orow = obase + (uint32_t)(gy * a.gw) * ldo_b;
+                if (c32o / OROWS == rnd) {
+#pragma unroll
+                    for (int db = 0; db < DB; ++db)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+                            if (db * 32 + g * 8 < HD) *reinterpret_cast<uint2*>(wslab + db * 64 + g * 16) = pk[db][g];
+                }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int t = 0; t < NCH; ++t) {
+                    if (64 * t + 64 <= OROWS * CPR || l6 < OROWS * CPR - 64 * t) {
+                        const uint4 v = *reinterpret_cast<const uint4*>(rslab + 1024 * t);
+                        *reinterpret_cast<uint4*>(orow + coff[t]) = v;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        } else {
             const int wy = w / nwx, wx = w - wy * nwx;
             bf16_t* obase = a.out + (int64_t)b * ntok * a.ldo + h * HD;
 #pragma unroll
@@ -666,6 +802,7 @@ extern "C" int swiftk_qkv_attention_fused(const void* x, int64_t ldx, const void
     if (((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)out & 15) || (ldx * 2) % 16 || (ldw * 2) % 16 || (ldo * 2) % 16)
         return SWIFTK_EALIGN;
     if ((int64_t)gh * gw * ldx * 2 >= (1ll << 32) || (int64_t)3 * head_dim * ldw * 2 >= (1ll << 32)) return SWIFTK_ESHAPE;
+    if ((int64_t)gh * gw * ldo * 2 >= (1ll << 32)) return SWIFTK_ESHAPE;  // a sample's output rows: 32-bit byte offsets in the kernel
     FusedArgs a;
     a.x = static_cast<const char*>(x);
     a.w = static_cast<const char*>(w);
@@ -683,15 +820,23 @@ extern "C" int swiftk_qkv_attention_fused(const void* x, int64_t ldx, const void
     int grid = g_persist_wgs >= 8 ? (g_persist_wgs & ~7) : g_persist_wgs;  // tuning key 2: one workgroup per CU the stream may use
     if (nitems < grid) grid = nitems >= 8 ? (nitems & ~7) : nitems;
     const bool timed = swiftk_prof_begin(SWIFTK_PROF_ATTENTION, 0, st);
-    if (g_attn_pp) {
-        if (head_dim == 80) hipLaunchKernelGGL((qkv_attn_kernel<80, true>), dim3(grid), dim3(NT), 0, st, a, nitems);
-        else if (head_dim == 96) hipLaunchKernelGGL((qkv_attn_kernel<96, true>), dim3(grid), dim3(NT), 0, st, a, nitems);
-        else hipLaunchKernelGGL((qkv_attn_kernel<88, true>), dim3(grid), dim3(NT), 0, st, a, nitems);
-    } else {
-        if (head_dim == 80) hipLaunchKernelGGL((qkv_attn_kernel<80, false>), dim3(grid), dim3(NT), 0, st, a, nitems);
-        else if (head_dim == 96) hipLaunchKernelGGL((qkv_attn_kernel<96, false>), dim3(grid), dim3(NT), 0, st, a, nitems);
-        else hipLaunchKernelGGL((qkv_attn_kernel<88, false>), dim3(grid), dim3(NT), 0, st, a, nitems);
-    }
+    const int grid_ = grid;
+    auto launch = [&](auto pp_tag, auto sl_tag) {
+        constexpr bool PP = decltype(pp_tag)::value;
+        constexpr int SL = decltype(sl_tag)::value;
+        if (head_dim == 80) hipLaunchKernelGGL((qkv_attn_kernel<80, PP, SL>), dim3(grid_), dim3(NT), 0, st, a, nitems);
+        else if (head_dim == 96) hipLaunchKernelGGL((qkv_attn_kernel<96, PP, SL>), dim3(grid_), dim3(NT), 0, st, a, nitems);
+        else hipLaunchKernelGGL((qkv_attn_kernel<88, PP, SL>), dim3(grid_), dim3(NT), 0, st, a, nitems);
+    };
+    auto launch_sl = [&](auto pp_tag) {
+        switch (g_attn_sl & 3) {  // tuning key 30
+            case 0: launch(pp_tag, std::integral_constant<int, 0>{}); break;
+            case 1: launch(pp_tag, std::integral_constant<int, 1>{}); break;
+            case 2: launch(pp_tag, std::integral_constant<int, 2>{}); break;
+            default: launch(pp_tag, std::integral_constant<int, 3>{}); break;
+        }
+    };
+    if (g_attn_pp) launch_sl(std::true_type{}); else launch_sl(std::false_type{});
     if (timed) swiftk_prof_end(st);
     SWIFTK_CHECK_LAUNCH();
     return 0;
