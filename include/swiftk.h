@@ -346,6 +346,13 @@ int swiftk_profile_gemm(int epilogue, int64_t N);
  *          block classes and store offsets resolved at compile time: no per-store exec region), bit 1 = straight-line output stage
  *          (scale + pack once per item, one exec region per 16-row round, 32-bit store offsets) and incremental item decode;
  *          0 = the round-3..6 forms.  Bit-equal results at every value (tools/qkv_handoff_probe.py times the four),
+ * key 31 = the persistent bf16 GEMM outside its k-loop (default 2; bf16 operands and output, SWIFTK_EPI_NONE and SWIFTK_EPI_SWIGLU,
+ *          352-wide tiles of the ping-pong kernel): bit 0 = straight-line epilogue of interior tiles (per-tile chunk offsets, wave-uniform
+ *          slab base, no per-store bounds check; an ldc of 2^27 elements or more is refused while the bit is set), bit 1 = the tile walk's
+ *          successor by adds and carries instead of divisions (unsplit products); 0 = the round-1..7 forms.  Bit-equal results at every
+ *          value (tools/gemm_epilogue_probe.py times the four),
+ * key 32 = diagnostic of key 31, for tests: bit n is set once swiftk_gemm has launched the SL = n instantiation of the 352-wide ping-pong
+ *          kernel (n = the bits of key 31 that applied; n = 0 the old forms); setting the key to any value clears the mask,
  * key 25 = clears through hipMemsetAsync instead of a kernel (0; diagnosis only; bit 1 = the library's internal clears --
  * swiftk_modnorm_bwd's workspace, swiftk_scm_target's scratch --, bit 2 = swiftk_zero_f32, bit 4 = a check kernel behind
  * swiftk_modnorm_bwd's clear records what it left non-zero: swiftk_zero_check_report). */

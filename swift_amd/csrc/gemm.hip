@@ -206,6 +206,22 @@ __device__ __forceinline__ void store16_out(void* p, const uint4& q) {
 #endif
 }
 
+// the same store from a wave-uniform base (a scalar register pair) plus a 32-bit per-lane byte offset: the straight-line epilogue's
+// form (tuning key 31 bit 0).  Written as asm because hipcc selects this addressing mode only where it sees the offset's zero-extension
+// in the store's own basic block -- past a slab's exec region it falls back to a 64-bit vector add per store.
+__device__ __forceinline__ void store16_out_sbase(char* base, uint32_t off, const uint4& q) {
+    const u32x4 v = {q.x, q.y, q.z, q.w};
+#if SWIFTK_X_STORE == 0
+    asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
+#elif SWIFTK_X_STORE == 1
+    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
+#elif SWIFTK_X_STORE == 2
+    asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
+#else
+    asm volatile("global_store_dwordx4 %0, %1, %2 sc0 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
+#endif
+}
+
 template <typename OutT>
 __device__ __forceinline__ void store2(OutT* p, float a, float b);
 template <>
@@ -482,8 +498,16 @@ struct TileIter {
     }
 };
 
-template <typename T, typename OutT, int EPI, int NI, bool PPK>
+// SL (tuning key 31; bf16 operands and output, SWIFTK_EPI_NONE / SWIFTK_EPI_SWIGLU, the 352-wide ping-pong instantiation): what a tile
+// costs OUTSIDE its k-loop, where no MFMA pipe of the CU is busy.  Bit 0 = straight-line epilogue of an interior tile (every address
+// term that depends on the lane alone is formed once per tile, the slab's global base is wave-uniform and advances by 16 rows, one exec
+// region per slab instead of one per store); bit 1 = the persistent walk's successor by adds and carries instead of divisions of the
+// tile number.  0 = the forms every other instantiation keeps.  Results are bit-equal at every value.
+template <typename T, typename OutT, int EPI, int NI, bool PPK, int SL = 0>
 __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm) {
+    constexpr bool SLE = (SL & 1) != 0, SLW = (SL & 2) != 0;
+    static_assert(SL == 0 || (sizeof(T) == 2 && sizeof(OutT) == 2 && PPK && (EPI == SWIFTK_EPI_NONE || EPI == SWIFTK_EPI_SWIGLU)),
+                  "the straight-line forms exist for the bf16 plain and SwiGLU epilogues of the ping-pong kernel only");
     // geometry of this instantiation: 8 waves as 4 (M) x 2 (N), each 64 x 16 NI
     constexpr int WT = 16 * NI;                 // columns of a wave tile (160 / 176 / 192)
     constexpr int BN = 2 * WT;                  // 320 / 352 / 384
@@ -499,6 +523,8 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     constexpr bool PAIRED = EPI == SWIFTK_EPI_QKNORM_JVP || EPI == SWIFTK_EPI_SWIGLU_JVP;
     // PPK: the ping-pong k-loop (needs at least three k-tiles per work item; the launcher checks)
     constexpr bool PP = PPK && sizeof(T) == 2 && !TOUCH && !HPF && !SWIFTK_GEMM_INSTR;
+    static_assert(SL == 0 || PP, "the straight-line forms are written into the ping-pong walk");
+    static_assert(SL == 0 || SWIFTK_X_VMCNT, "the straight-line epilogue takes the interior test of the counted store wait");
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + (TOUCH || HPF ? 256 : 0)];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -515,7 +541,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     // k-halves, split s into slab s.  tail_from is a multiple of the grid size and at most half a round of tiles follows it, so the
     // round-robin walk below hands every workgroup its whole tiles and then at most ONE half: the last round costs half a tile time
     constexpr bool TAIL = EPI == EPI_NONE_TAIL;
-    const int ksplit = TAIL ? 1 : g.ksplit;
+    const int ksplit = TAIL || SLW ? 1 : g.ksplit;  // (SLW: the launcher takes the incremental walk for unsplit products only)
     const int tail_from = TAIL ? g.tail_from : 0;
     const int ntiles = TAIL ? 2 * ntm * g.ntn - tail_from : ntm * g.ntn * ksplit;
     auto tile_of = [&](int item) {
@@ -561,6 +587,44 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
         else return (int)((int64_t)(item % ksplit + 1) * nk_all / ksplit);
     };
     int tile = vid, kt = k_begin(vid);
+    // SLW: the walk in mixed radix, tile = (w_grp * ntn + w_tn) * gm + w_rr, and the grid stride in the same radix -- the successor
+    // is three adds with two carries.  A full group reads its coordinates off the digits; only the short last group of the walk
+    // (ntm % gm rows) divides, as the first tile does.  n_tm / n_tn: the tile the DMA is about to feed; c_tm / c_tn: the one in its epilogue.
+    int w_grp = 0, w_tn = 0, w_rr = 0, s_grp = 0, s_tn = 0, s_rr = 0, n_tm = 0, n_tn = 0, c_tm = 0, c_tn = 0;
+    if constexpr (SLW) {
+        const int per = gm * g.ntn;
+        w_grp = vid / per;
+        int r = vid - w_grp * per;
+        w_tn = r / gm;
+        w_rr = r - w_tn * gm;
+        s_grp = stride / per;
+        r = stride - s_grp * per;
+        s_tn = r / gm;
+        s_rr = r - s_tn * gm;
+    }
+    auto walk_coords = [&](int& tm, int& tn) {
+        const int rows = ntm - w_grp * gm;
+        tm = w_grp * gm + w_rr;
+        tn = w_tn;
+        if (rows < gm) {
+            const int r = w_tn * gm + w_rr;
+            tn = r / rows;
+            tm = w_grp * gm + (r - tn * rows);
+        }
+    };
+    auto walk_step = [&] {
+        w_rr += s_rr;
+        int c = w_rr >= gm;
+        w_rr -= c ? gm : 0;
+        w_tn += s_tn + c;
+        c = w_tn >= g.ntn;
+        w_tn -= c ? g.ntn : 0;
+        w_grp += s_grp + c;
+    };
+    auto src_coords = [&](int t, int& tm, int& tn) {
+        if constexpr (SLW) { tm = n_tm; tn = n_tn; }
+        else it.coords(tile_of(t), tm, tn);
+    };
     // Row bases of this wave's ten pieces for the tile the DMA currently feeds: computed once per tile and kept in
     // SGPRs, so issuing a piece costs three instructions (M0, nop, load) instead of ~20 scalar address ops -- at
     // ten pieces per k-tile the scalar arithmetic alone used to take as many issue slots as the 88 MFMAs.
@@ -604,7 +668,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     auto w1row = [&](int i) { const int n = wv + 8 * i, h = n >= 2 * JB; return h * WT + JA * 16 + (n - 2 * JB * h) * 8; };
     auto set_sources_aw1 = [&](int t) {
         int tm, tn;
-        it.coords(tile_of(t), tm, tn);
+        src_coords(t, tm, tn);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             int rb = tm * BM + (wv * 4 + p) * 8;
@@ -621,7 +685,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     };
     auto set_sources_w0 = [&](int t) {
         int tm, tn;
-        it.coords(tile_of(t), tm, tn);
+        src_coords(t, tm, tn);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             int rb = tn * BN + w0row(i);
@@ -672,6 +736,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     // the other; past the very last step the "following step" is a harmless re-load of this tile's first k-tile.
     int nk = k_end(tile);
     if constexpr (PP) {
+        if constexpr (SLW) walk_coords(n_tm, n_tn);
         set_sources_aw1(tile);
         set_sources_w0(tile);
 #pragma unroll
@@ -785,6 +850,11 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
         if constexpr (PP) {
             const int ntile = tile + stride < ntiles ? tile + stride : tile;  // (past the last item: harmless re-loads)
             if (last_k) {
+                if constexpr (SLW) {
+                    walk_coords(c_tm, c_tn);
+                    if (ntile != tile) walk_step();
+                    walk_coords(n_tm, n_tn);
+                }
                 set_sources_aw1(ntile);
                 set_sources_w0(ntile);
                 koff = (uint32_t)k_begin(ntile) * ROWB;
@@ -1060,7 +1130,8 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
 #endif
         {
             int tm, tn;
-            it.coords(tile_of(tile), tm, tn);
+            if constexpr (SLW) { tm = c_tm; tn = c_tn; }
+            else it.coords(tile_of(tile), tm, tn);
             const int m0 = tm * BM, n0 = tn * BN;
             if constexpr (EPI == SWIFTK_EPI_QKNORM || EPI == EPI_QKNORM_TILED)
                 qknorm_tile<NI>(acc, lane, n0 + wn * WT, g.ep0, const_cast<float*>(g.ep1), m0 + wm * 64, g.M, g.N / HD, sizeof(T) == 4 && g.qk_only);
@@ -1077,9 +1148,9 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                 // wave's slab, rows leaving as whole 16-B chunks like every bf16 tile
                 constexpr int RS1 = WT * 2 + 16, RS2 = WT + 16;  // padded slab row strides (bytes): WT / WT/2 columns
                 constexpr int CP1 = WT / 8, CP2 = WT / 16;       // 16-B chunks per row
-                constexpr int SL = 16 * RS1 > 32 * RS2 ? 16 * RS1 : 32 * RS2;
+                constexpr int SLB = 16 * RS1 > 32 * RS2 ? 16 * RS1 : 32 * RS2;  // slab bytes per wave
                 __builtin_amdgcn_s_barrier();
-                char* slab = const_cast<char*>(s) + wv * SL;
+                char* slab = const_cast<char*>(s) + wv * SLB;
                 int elane = lane;
                 asm volatile("" : "+v"(elane));
                 const int g4 = elane >> 4;
@@ -1315,6 +1386,68 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                 const int ncol0 = (GLU ? (n0 >> 1) : n0) + wn * COLS;
                 const int nout = GLU ? (g.N >> 1) : g.N;
                 uint32_t lo_pk[SPLIT3 || PAIROUT ? NI : 1];  // SPLIT3 / PAIROUT: the low parts of this row block's (hi, lo) pairs
+                bool sl_done = false;
+                if constexpr (SLE) {
+                    // Straight-line form of an interior tile (tuning key 31 bit 0): the same values, packed, parked and stored in the
+                    // same order as below.  The lane id stays opaque (nothing of this is hoisted above the k-loop) but what is derived
+                    // from it is masked, so the slab writes are one base register plus immediates; a chunk's (row, column) is a function
+                    // of the lane and t alone and is formed once per tile as one LDS offset and one 32-bit global byte offset; the
+                    // slab's global base is wave-uniform (scalar registers) and advances by 16 rows; no store carries a bounds check,
+                    // the only exec region is the partial last chunk's lane mask.  Edge tiles take the predicated loop below.
+                    if (interior) {
+                        int el = lane;
+                        asm volatile("" : "+v"(el));
+                        const int sr16 = el & 15, sg4 = (el >> 4) & 3, l64 = el & 63;
+                        constexpr int NCH = (16 * CPR + 63) / 64;
+                        constexpr bool PART = (16 * CPR) % 64 != 0;
+                        char* wr = slab + sr16 * RSTR + sg4 * (GLU ? 4 : 8);
+                        const uint32_t ldcb = (uint32_t)g.ldc * 2u;  // (16 rows of C fit in 32 bits of byte offset: the entry point checks)
+                        uint32_t ro[NCH], go[NCH];
+#pragma unroll
+                        for (int t = 0; t < NCH; ++t) {
+                            const int c = l64 + 64 * t;
+                            const int row = c / CPR, cc = c - row * CPR;
+                            ro[t] = (uint32_t)(row * RSTR + cc * 16);
+                            go[t] = (uint32_t)row * ldcb + (uint32_t)(cc * 16);
+                        }
+                        const bool part_on = l64 + 64 * (NCH - 1) < 16 * CPR;
+                        char* cb = reinterpret_cast<char*>(C) + ((int64_t)(m0 + wm * 64) * g.ldc + ncol0) * 2;
+#pragma unroll
+                        for (int i = 0; i < MI; ++i) {
+#pragma unroll
+                            for (int j = 0; j < NI; ++j) {
+                                const f32x4 v = acc[i][j];
+                                acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                                if constexpr (GLU) {
+#if SWIFTK_X_NOSILU
+                                    const float h0 = v[0] * v[1];
+                                    const float h1 = v[2] * v[3];
+#else
+                                    const float h0 = v[0] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[0])) * v[1];
+                                    const float h1 = v[2] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[2])) * v[3];
+#endif
+                                    *reinterpret_cast<uint32_t*>(wr + j * 16) = pack_bf16(h0, h1);
+                                } else {
+                                    *reinterpret_cast<uint2*>(wr + j * 32) = make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
+                                }
+                            }
+                            __builtin_amdgcn_wave_barrier();
+                            // all of the slab's chunks are requested before the first store (an asm store orders memory operations around
+                            // it); the partial chunk's idle lanes read LDS bytes behind the slab, which stay inside the stage
+                            uint4 q[NCH];
+#pragma unroll
+                            for (int t = 0; t < NCH; ++t) q[t] = *reinterpret_cast<const uint4*>(slab + ro[t]);
+#pragma unroll
+                            for (int t = 0; t < NCH; ++t) {
+                                if (!PART || t + 1 < NCH || part_on) store16_out_sbase(cb, go[t], q[t]);
+                            }
+                            __builtin_amdgcn_wave_barrier();
+                            cb += (int64_t)g.ldc * 32;
+                        }
+                        sl_done = true;
+                    }
+                }
+                if (!sl_done)
 #pragma unroll
                 for (int ii = 0; ii < MI; ++ii) {
                     // QKNORM_JVP: a tangent row block leaves before its primal block (2, 0, 3, 1) -- its rule reads the primal values
@@ -1570,6 +1703,10 @@ int g_group_m = 8;   // tile rows per group in the persistent order
 int g_dbg = 0;
 int g_stagger_permille = 0;  // tuning key 7: start-up phase step as a fraction (in 1/1000) of an eighth of the estimated tile time
 int g_pp = SWIFTK_X_PP;      // tuning key 20: ping-pong k-loop of the persistent kernel (bf16 operands)
+// tuning key 31: gemm_kernel_p outside its k-loop (SL): bit 0 straight-line epilogue, bit 1 incremental tile walk.  A bit ships set where
+// its slowest round beat the old arm's fastest in tools/gemm_epilogue_probe.py: bit 1 did on wo, w1 + SwiGLU and w2 (-1.7 ... -2.0 %), bit 0
+// did not on wo and w1 + SwiGLU (profiles/r08a_gemm_epilogue_straightline.txt) and stays selectable only
+int g_gemm_sl = 2;
 
 // the ping-pong loop prefetches W0 two k-tiles ahead: every work item needs at least three k-tiles
 inline bool pp_ok(const GemmArgs& g) { return g_pp > 0 && !SWIFTK_GEMM_INSTR && (g.K / 64) / g.ksplit >= 3; }
@@ -1580,6 +1717,32 @@ struct Prof {
     hipEvent_t ev[2 * MAXE];
     int created = 0, used = 0;
 } g_prof;
+
+// the instantiations that take the straight-line forms of tuning key 31 (see SL at gemm_kernel_p)
+template <typename T, typename OutT, int EPI>
+constexpr bool sl_capable = sizeof(T) == 2 && sizeof(OutT) == 2 && (EPI == SWIFTK_EPI_NONE || EPI == SWIFTK_EPI_SWIGLU) &&
+                            // (written into the ping-pong walk and the counted store wait: not in the builds that compile either out)
+                            !SWIFTK_GEMM_INSTR && !(SWIFTK_X_TOUCH > 0) && SWIFTK_X_VMCNT;
+int g_gemm_sl_seen = 0;  // tuning key 32 (diagnostic): bit n = the SL = n instantiation was launched since the key was last cleared
+
+// 352-wide tiles, ping-pong k-loop: the one geometry of the forecast step's wo / w1 / w2 products
+template <typename T, typename OutT, int EPI>
+int launch_p11_pp(const GemmArgs& g, int grid, int ntm, hipStream_t st) {
+    if constexpr (sl_capable<T, OutT, EPI>) {
+        // straight-line epilogue: a slab's 16 rows are addressed by a 32-bit byte offset from a wave-uniform base
+        if ((g_gemm_sl & 1) && g.ldc >= (int64_t(1) << 27)) return SWIFTK_ESHAPE;
+        // (the incremental walk is written for one k-range per tile)
+        const int sl = g_gemm_sl & (g.ksplit == 1 ? 3 : 1);
+        g_gemm_sl_seen |= 1 << sl;
+        switch (sl) {
+            case 1: hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, true, 1>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m); return 0;
+            case 2: hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, true, 2>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m); return 0;
+            case 3: hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, true, 3>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m); return 0;
+        }
+    }
+    hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
+    return 0;
+}
 
 template <typename T, typename OutT, int EPI>
 int launch(const GemmArgs& g, hipStream_t st) {
@@ -1606,7 +1769,7 @@ int launch(const GemmArgs& g, hipStream_t st) {
             if (pp_ok(g)) {
                 if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 10, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
                 else if (g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 12, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-                else hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
+                else if (const int rc = launch_p11_pp<T, OutT, EPI>(g, grid, ntm, st)) return rc;
             } else {
                 if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 10, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
                 else if (g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 12, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
@@ -1729,6 +1892,8 @@ extern "C" int swiftk_set_tuning(int key, int value) {
         case 28: g_x3_attnpv = value; return 0;
         case 29: g_fwd_tail = value; return 0;
         case 30: g_attn_sl = value & 3; return 0;
+        case 31: g_gemm_sl = value & 3; return 0;
+        case 32: g_gemm_sl_seen = 0; return 0;
         case 25:
             g_zero_memset = value;
             return (value & 4) ? swiftk_zero_check_enable() : 0;
@@ -1767,6 +1932,8 @@ extern "C" int swiftk_get_tuning(int key) {
         case 28: return g_x3_attnpv;
         case 29: return g_fwd_tail;
         case 30: return g_attn_sl;
+        case 31: return g_gemm_sl;
+        case 32: return g_gemm_sl_seen;
     }
     return SWIFTK_EINVAL;
 }
