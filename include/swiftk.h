@@ -200,7 +200,8 @@ int swiftk_gemm_modnorm_residual_pair(const void* A, int64_t lda, const void* W,
                                       int64_t ldmod, int64_t M, int d, int64_t rows_per_sample, float eps,
                                       int rows_per_workgroup, void* stream);
 /* fp32 [rows, lds] -> the pair form: hi [rows, ldh] bf16 with columns [cols, ldh) zeroed (GEMM k-padding), lo [rows, ldl]
- * (bf16 or uint8 by lo_bits, ldl in elements). */
+ * (bf16 or uint8 by lo_bits, ldl in elements).  Refused: lo_bits other than 16 / 8 (SWIFTK_EINVAL); cols, lds, ldh or ldl not a
+ * multiple of 4, or a row stride below cols (SWIFTK_ESHAPE); src off a 16-byte boundary, hi or lo off an 8-byte one (SWIFTK_EALIGN). */
 int swiftk_split_pair(const float* src, int64_t lds, void* hi, int64_t ldh, void* lo, int64_t ldl, int lo_bits, int64_t rows,
                       int64_t cols, void* stream);
 /* The patch embedding straight into the pair form (round 4): what swiftk_gemm(..., SWIFTK_EPI_BIAS_POS, bias, pos, pos_rows) with fp32
@@ -225,9 +226,12 @@ int swiftk_patchify_scaled(const float* src0, int c0, float s0, const float* s0_
 
 /*
  * out[b][c][y][x] = alpha[b] * xt[b][c][y][x] + beta[b] * tok[b][gy*gw+gx][(c*p1+i1)*p2+i2]
- * (xt may be NULL -> alpha ignored).  Replaces swinv2.py:241-243 (un-patchify)
+ * (xt may be NULL -> alpha ignored).  alpha == NULL means alpha[b] = 0, beta == NULL means beta[b] = 1 (with neither and no xt
+ * the output is the gathered token value, bit for bit).  Replaces swinv2.py:241-243 (un-patchify)
  * fused with the sampler update cos(t) x_t - sin(t) sigma_d F (diffusion.py:459).
- *   tok [B, gh*gw, ldt] fp32
+ *   tok [B, gh*gw, ldt] fp32, ldt >= C*p1*p2 (columns behind C*p1*p2 are never read); any patch shape, any alignment
+ *   (2 x 2 patches with W % 4 == 0, an even ldt, tok on an 8-byte and xt / out on a 16-byte boundary take a vector kernel;
+ *   same bits either way)
  */
 int swiftk_unpatchify_affine(const float* tok, int64_t ldt, const float* xt, const float* alpha, const float* beta,
                              float* out, int B, int C, int H, int W, int p1, int p2, void* stream);
@@ -235,7 +239,9 @@ int swiftk_unpatchify_affine(const float* tok, int64_t ldt, const float* xt, con
 /*
  * Sinusoidal timestep embedding + auxiliary embedding:
  *   emb[b][i] = sin(t_b w f_i) (i < d/2) | cos(t_b w f_{i-d/2})  + aux_w[i][:] . aux[b][:] sqrt(aux_dim) + aux_b[i]
- * Replaces swinv2.py:44-60 and :318-320.  freqs [d/2] fp32 is supplied by the host.
+ * Replaces swinv2.py:44-60 and :318-320.  freqs [d/2] fp32 is supplied by the host.  The argument is formed in fp32 as
+ * (t_b * w) * f_i and goes through the full-range sinf / cosf.  Odd d: [sin | cos | 0] over d/2 + d/2 + 1 columns (the zero
+ * column is last; the aux part is added to it as to the others).
  */
 int swiftk_timestep_embed(const float* t, const float* aux, const float* freqs, const float* aux_w, const float* aux_b,
                           float* emb, int B, int d, int aux_dim, float timestep_weight, void* stream);
@@ -244,6 +250,9 @@ int swiftk_timestep_embed(const float* t, const float* aux, const float* freqs, 
  * Small-batch fp32 linear: out[b][n] = act(x[b][:] . W[n][:] + bias[n]) (any B; rows are walked 8 at a time).
  * act: 0 none, 1 SiLU.  Replaces swinv2.py:74 (LatentEmbedding), :85
  * (all modulation Linears, concatenated along n), :327 (logvar).
+ *   x [B, ldx], W [N, ldw], out [B, ldo] fp32; bias [N] or NULL (= 0); columns behind K / N are neither read nor written.
+ * Refused with SWIFTK_EALIGN: x or W off a 16-byte boundary, ldx or ldw not a multiple of 4 (rows are read as 16-byte
+ * vectors; K itself may be any size -- a K % 4 tail is read element by element).  out and ldo carry no condition.
  */
 int swiftk_linear_small(const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* out,
                         int64_t ldo, int B, int N, int K, int act, void* stream);
@@ -268,7 +277,9 @@ int swiftk_counter_add(int64_t* counter, int64_t value, void* stream);
  * Residual rollout update in physical units, fused with re-standardisation:
  *   phys[b][c] = xstd[b][c]*sx[c] + mx[c] + y[b][c]*st[c];  xstd[b][c] = (phys[b][c] - mx[c]) / sx[c]
  * Replaces generate.py:120-131 with data/era5.py:110-166.  st == NULL selects the non-residual form of generate.py:132-136
- * (a dataset whose targets are states, not tendencies): phys = y*sx + mx; xstd = y.
+ * (a dataset whose targets are states, not tendencies): phys = y*sx + mx (two roundings, no fused multiply-add: bit equal to the
+ * reference's fp32 expression); xstd = y.  phys may be NULL (not written).  A channel with sx[c] == 0 gets xstd = +0.
+ * Refused: hw not a multiple of 4 (SWIFTK_ESHAPE); xstd, y or phys off a 16-byte boundary (SWIFTK_EALIGN).
  */
 int swiftk_rollout_update(float* xstd, const float* y, float* phys, const float* mx, const float* sx, const float* st,
                           int B, int C, int64_t hw, void* stream);
@@ -278,13 +289,15 @@ int swiftk_rollout_update(float* xstd, const float* y, float* phys, const float*
  * generate.py:139-152, and has no collective): out[b] = fp64 sum of unit b's n fp32 values, added in a
  * fixed order -- bit-identical for a unit whatever rank or batch slot computed it, so ranks can
  * all-gather B doubles per step instead of 9 MB per unit.  scratch: 32*B doubles.
+ * Refused: n not a multiple of 4 (SWIFTK_ESHAPE); x off a 16-byte boundary (SWIFTK_EALIGN).
  */
 int swiftk_unit_checksum(const float* x, double* out, double* scratch, int B, int64_t n, void* stream);
 
 /*
- * out = a*x + b*y (fp32, out may alias x or y): the samplers' state arithmetic between network
- * evaluations -- re-noising sin(t) sigma_d eps + cos(t) x (diffusion.py:454-455) and the Heun
- * average (diffusion.py:411).
+ * out = a*x + b*y (fp32, out may BE x or y -- the same pointer; partly overlapping ranges are not supported): the samplers'
+ * state arithmetic between network evaluations -- re-noising sin(t) sigma_d eps + cos(t) x (diffusion.py:454-455) and the Heun
+ * average (diffusion.py:411).  Any n > 0 (an n % 4 tail is done element by element).
+ * Refused with SWIFTK_EALIGN: out, x or y off a 16-byte boundary.
  */
 int swiftk_axpby(float* out, float a, const float* x, float b, const float* y, int64_t n, void* stream);
 
@@ -578,7 +591,9 @@ int swiftk_channel_axpy(float* out, const float* x, const float* y, const float*
 /* fp32 -> three bf16 column blocks of `cols` columns each (cols % 4 == 0, ldd >= 3*cols, the rest of a row zero):
  * hi = bf16(v), lo = bf16(v - hi).  order 0: [hi | lo | hi] (activations), order 1: [hi | hi | lo] (weights) -- the operand
  * layout of the SWIFTK_BF16X3 engine: swiftk_gemm over K' = 3*cols on these is hi hi' + lo hi' + hi lo' in fp32 accumulators,
- * an fp32-grade product (measured 4.5e-6 relative against fp64) at the bf16 MFMA rate / 3. */
+ * an fp32-grade product (measured 4.5e-6 relative against fp64) at the bf16 MFMA rate / 3.
+ * Refused: order other than 0 / 1, lds < cols or ldd < 3*cols (SWIFTK_EINVAL); cols, lds or ldd not a multiple of 4 (SWIFTK_ESHAPE);
+ * src off a 16-byte boundary or dst off an 8-byte one (SWIFTK_EALIGN). */
 int swiftk_split3(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t cols, int order, void* stream);
 
 /* fp32 -> dtype copy with row padding: dst[r][c] = src[r][c] for c < cols, 0 for cols <= c < ldd. */

@@ -1045,8 +1045,9 @@ __global__ __launch_bounds__(256) void rollout_update_kernel(float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void axpby_kernel(float* __restrict__ out, float a, const float* __restrict__ x, float b,
-                                                    const float* __restrict__ y, int64_t n4, int64_t n) {
+// (no __restrict__: out may be x or y -- every thread reads the elements it writes before it writes them)
+__global__ __launch_bounds__(256) void axpby_kernel(float* out, float a, const float* x, float b, const float* y, int64_t n4,
+                                                    int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const float4 xv = reinterpret_cast<const float4*>(x)[i];
         const float4 yv = reinterpret_cast<const float4*>(y)[i];

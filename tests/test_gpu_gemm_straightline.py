@@ -3,9 +3,16 @@ tile walk (bit 1) against the forms they replace (key 31 = 0), bit for bit, at t
 several tiles per workgroup (the slab base's advance, the walk's successor across the grouped order, the counted store wait between
 tiles, the ping-pong loop's minimum of three k-tiles, the half k-tile), edge tiles beside interior ones in one launch (the predicated
 cold path), and a last row group shorter than the group height.  The output sits in a buffer wider than the product, pre-filled with a
-sentinel that every arm must leave alone."""
+sentinel that every arm must leave alone.
+
+The walk cases (tests/layout_reference.py, WALK_CASES; K = 192, whole 256 x 352 tiles) set the group height (tuning key 1) and the
+workgroup count (key 2) so that the mixed-radix successor takes what no default launch does: a non-zero row digit of the stride, the
+first carry, both carries in one step, a carrying step into the short last group, a row digit of radix 1, a walk whose only group is
+short, and a single column tile.  tests/test_layout_reference_cpu.py checks that each case takes the carries its name claims."""
 import pytest
 import torch
+
+from layout_reference import WALK_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -28,19 +35,19 @@ def _operands(dev, M, N, K, ldk, seed):
     return a, w
 
 
-# (epilogue, M, N, K, row stride of the operands, workgroups (tuning key 2) or None for the default grid)
+# (epilogue, M, N, K, row stride of the operands, workgroups (tuning key 2) or None for the default grid, group height (tuning key 1))
 CASES = [
-    pytest.param("none", 1024, 1056, 192, 192, 8, id="interior-plain-12-tiles-on-8"),
-    pytest.param("swiglu", 1024, 1408, 1056, 1088, 8, id="interior-swiglu-16-tiles-on-8-half-k-tile"),
-    pytest.param("none", 304, 536, 192, 192, None, id="edges-plain"),
-    pytest.param("swiglu", 304, 528, 1056, 1088, None, id="edges-swiglu"),
-    pytest.param("none", 2304, 704, 192, 192, 8, id="short-last-group-plain"),
-    pytest.param("swiglu", 2304, 704, 1056, 1088, 8, id="short-last-group-swiglu"),
-]
+    pytest.param("none", 1024, 1056, 192, 192, 8, 8, id="interior-plain-12-tiles-on-8"),
+    pytest.param("swiglu", 1024, 1408, 1056, 1088, 8, 8, id="interior-swiglu-16-tiles-on-8-half-k-tile"),
+    pytest.param("none", 304, 536, 192, 192, None, 8, id="edges-plain"),
+    pytest.param("swiglu", 304, 528, 1056, 1088, None, 8, id="edges-swiglu"),
+    pytest.param("none", 2304, 704, 192, 192, 8, 8, id="short-last-group-plain"),
+    pytest.param("swiglu", 2304, 704, 1056, 1088, 8, 8, id="short-last-group-swiglu"),
+] + [pytest.param(c.epi, c.M, c.N, 192, 192, c.wgs, c.gm, id="walk-" + c.name) for c in WALK_CASES]
 
 
-@pytest.mark.parametrize("epi, M, N, K, ldk, wgs", CASES)
-def test_key31_arms_equal_old_forms(dev, epi, M, N, K, ldk, wgs):
+@pytest.mark.parametrize("epi, M, N, K, ldk, wgs, gm", CASES)
+def test_key31_arms_equal_old_forms(dev, epi, M, N, K, ldk, wgs, gm):
     from swift_amd import _lib
     L = _lib.lib()
     st = torch.cuda.current_stream().cuda_stream
@@ -54,6 +61,8 @@ def test_key31_arms_equal_old_forms(dev, epi, M, N, K, ldk, wgs):
     try:
         if wgs is not None:
             _lib.check(L.swiftk_set_tuning(2, wgs), "swiftk_set_tuning")
+        _lib.check(L.swiftk_set_tuning(1, gm), "swiftk_set_tuning")
+        assert L.swiftk_get_tuning(1) == gm
         for arm in (0, 1, 2, 3):
             _lib.check(L.swiftk_set_tuning(31, arm), "swiftk_set_tuning")
             assert L.swiftk_get_tuning(31) == arm
@@ -69,6 +78,7 @@ def test_key31_arms_equal_old_forms(dev, epi, M, N, K, ldk, wgs):
     finally:
         L.swiftk_set_tuning(31, key31)
         L.swiftk_set_tuning(2, key2)
+        L.swiftk_set_tuning(1, group_m)
     ref = outs[0]
     # the old arm is the reference; it is itself the product (fp32 accumulation of the bf16 operands, one rounding to bf16: half an
     # ulp = 2^-9 relative, doubled for the SwiGLU epilogue's exp / rcp at 1 ulp of fp32 each and its three products)
@@ -81,7 +91,13 @@ def test_key31_arms_equal_old_forms(dev, epi, M, N, K, ldk, wgs):
         assert bool((outs[arm][:, ncol:] == SENTINEL).all()), f"key 31 = {arm} wrote past column {ncol}"
         assert bool((outs[arm][M:] == SENTINEL).all()), f"key 31 = {arm} wrote past row {M}"
     for arm in (1, 2, 3):
-        assert torch.equal(outs[arm].view(torch.int16), ref.view(torch.int16)), f"key 31 = {arm} differs from key 31 = 0"
+        if not torch.equal(outs[arm].view(torch.int16), ref.view(torch.int16)):
+            bad = torch.nonzero(outs[arm].view(torch.int16) != ref.view(torch.int16))
+            r, c = int(bad[0][0]), int(bad[0][1])
+            msg = (f"key 31 = {arm} differs from key 31 = 0 in {bad.shape[0]} elements, first at (row, column) ({r}, {c}) = tile "
+                   f"(row, column) ({r // 256}, {c // (176 if epi == 'swiglu' else 352)})")
+            print(msg)
+            raise AssertionError(msg)
 
 
 def test_key31_is_a_two_bit_mask(dev):
