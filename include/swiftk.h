@@ -559,6 +559,23 @@ int swiftk_scm_target(const float* F, const float* dxt, const float* xt_over_sd,
  * slice).  The caller zero-fills sq (1 + C floats), divides by the counts and takes the roots. */
 int swiftk_rmse_sums(const float* y, const float* t, int64_t t_batch_stride, const float* w_lat, float* sq, int B, int C, int H,
                      int W, void* stream);
+/* Sampler-sweep scores (eval/sampler.py:97-105 with data/era5.py:110-133): per (sample, channel) the latitude-weighted sum of
+ * squared forecast errors in physical units, out[b][c] = sum_{h,w} w_lat[h] * (double)q with, in fp32 and rounding by rounding
+ * as the reference's numpy expression (no fused multiply-add anywhere),
+ *   xp = fl(fl(x sx[c]) + mx[c]),  yp = fl(xp + fl(y st[c])),  tp = fl(xp + fl(t st[c])),  d = fl(yp - tp),  q = fl(d d)
+ * xstd [B, >= C, H, W] with batch stride x_batch_stride (the first C channels of the network's condition are the residual
+ * base); y, t [B, C, H, W] contiguous standardised residuals; sx[c] == 0 gives xp = mx[c] (the zeroed SST channel, as in
+ * swiftk_rollout_update); w_lat [H] fp64.  The terms are added in fp64 in an order that depends on (H, W) only -- slice s of
+ * SWIFTK_SWEEP_SLICES covers float4s [s per, (s + 1) per) of the plane, per = ceil(H W / 4 / SWIFTK_SWEEP_SLICES); a lane adds
+ * its float4s in index order, the 64 lanes meet in a fixed xor tree, the 4 waves in wave order, the slices in slice order --
+ * so a sample's row has the same bits whatever B, batch slot or rank it was scored in.  No atomics: out [B, C] and scratch
+ * [B, C, SWIFTK_SWEEP_SLICES] (doubles) are written completely by every call and need no clearing.
+ * Refused before any launch: a null pointer, a non-positive size or x_batch_stride < C H W (SWIFTK_EINVAL); W not a multiple
+ * of 4, B or C above 65535 (SWIFTK_ESHAPE); xstd, y or t off a 16-byte boundary, x_batch_stride not a multiple of 4, a
+ * double pointer off an 8-byte boundary (SWIFTK_EALIGN). */
+#define SWIFTK_SWEEP_SLICES 8
+int swiftk_sweep_sse(const float* xstd, int64_t x_batch_stride, const float* y, const float* t, const float* mx, const float* sx,
+                     const float* st, const double* w_lat, double* out, double* scratch, int B, int C, int H, int W, void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
  * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host. */

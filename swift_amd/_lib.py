@@ -21,6 +21,7 @@ EPI_QKNORM_JVP, EPI_SWIGLU_JVP = 8, 9  # swiftk_gemm_jvp only
 EPI_SWIGLU_SPLIT3 = 10
 ATTN_PRENORM, ATTN_NO_PIPE, ATTN_TILED = 1, 2, 4
 PROF_ATTENTION = 100
+SWEEP_SLICES = 8  # SWIFTK_SWEEP_SLICES: partial sums per (sample, channel) in swiftk_sweep_sse's scratch
 
 _ERR = {-1: "SWIFTK_EINVAL (bad argument)", -2: "SWIFTK_ESHAPE (unsupported shape)",
         -3: "SWIFTK_EALIGN (misaligned pointer / leading dimension)", -4: "SWIFTK_EWORKSPACE (workspace too small)"}
@@ -125,6 +126,7 @@ _SIGS = {
     "swiftk_gemm_jvp": ([_p, _l, _p, _l, _p, _l, _l, _l, _l, _i, _p, _p, _i, _p, _l, _p], _i),
     "swiftk_ensemble_sums": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_rmse_sums": ([_p, _p, _l, _p, _p, _i, _i, _i, _i, _p], _i),
+    "swiftk_sweep_sse": ([_p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "swiftk_scm_target": ([_p, _p, _p, _p, _p, _f, _f, _p, _p, _i, _l, _p], _i),
     "swiftk_gemm_qkv_tiled": ([_p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_qkv_attention_fused": ([_p, _l, _p, _l, _p, _p, _l, _l, _i, _i, _i, _i, _i, _i, _i, _p], _i),

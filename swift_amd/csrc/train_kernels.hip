@@ -872,6 +872,64 @@ __global__ __launch_bounds__(256) void rmse_sums_kernel(const float* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------ sampler-sweep squared errors
+// out[b][c] = sum_{h,w} w_lat[h] * ((xp + y st) - (xp + t st))^2 with xp = x sx + mx: eval/sampler.py:97-105 with
+// data/era5.py:110-133, every fp32 rounding of the reference's numpy expression kept (contraction off where the arithmetic
+// is: no fused multiply-add), the weighted terms added in fp64 in an order that depends on (H, W) alone.  One workgroup per (slice, channel,
+// sample): slice s covers the float4 range [s per, (s + 1) per) of the plane, per = ceil(H W / 4 / SWEEP_SLICES); a lane adds
+// its float4s in index order, lanes meet in a fixed xor tree, waves in wave order through LDS; the finishing kernel adds the
+// SWEEP_SLICES partials in slice order.  Every element of `part` and `out` is written by every call: no atomics, no clear.
+constexpr int SWEEP_SLICES = SWIFTK_SWEEP_SLICES;
+__device__ __forceinline__ double sweep_term(float x, float y, float t, float m, float s, float r, double w) {
+#pragma clang fp contract(off)  // every product is rounded before it is added, as numpy rounds it (hipcc contracts by default)
+    const float xs = x * s;
+    const float xp = s == 0.f ? m : xs + m;  // (s == 0: a channel whose standardised value is forced to 0)
+    const float yr = y * r, tr = t * r;
+    const float yp = xp + yr, tp = xp + tr;
+    const float d = yp - tp;
+    const float q = d * d;
+    return w * (double)q;
+}
+__global__ __launch_bounds__(256) void sweep_sse_part_kernel(const float* __restrict__ xstd, int64_t x_batch_stride,
+                                                             const float* __restrict__ y, const float* __restrict__ t,
+                                                             const float* __restrict__ mx, const float* __restrict__ sx,
+                                                             const float* __restrict__ st, const double* __restrict__ w_lat,
+                                                             double* __restrict__ part, int C, int H, int W) {
+    __shared__ double red[4];
+    const int s = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int64_t hw = (int64_t)H * W, n4 = hw >> 2, per = (n4 + SWEEP_SLICES - 1) / SWEEP_SLICES;
+    const int64_t lo = s * per, hi = min(n4, lo + per);
+    const int w4 = W >> 2;
+    const float4* xs = reinterpret_cast<const float4*>(xstd + b * x_batch_stride + c * hw);
+    const float4* ys = reinterpret_cast<const float4*>(y + ((int64_t)b * C + c) * hw);
+    const float4* ts = reinterpret_cast<const float4*>(t + ((int64_t)b * C + c) * hw);
+    const float m = mx[c], sc = sx[c], r = st[c];
+    double acc = 0.0;
+#pragma unroll 4
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+#pragma clang fp contract(off)  // acc + w q: the product is rounded before it is added
+        const float4 xv = xs[i], yv = ys[i], tv = ts[i];
+        const double w = w_lat[(uint32_t)i / (uint32_t)w4];  // (W % 4 == 0: a float4 never straddles two latitude rows)
+        acc = acc + sweep_term(xv.x, yv.x, tv.x, m, sc, r, w);
+        acc = acc + sweep_term(xv.y, yv.y, tv.y, m, sc, r, w);
+        acc = acc + sweep_term(xv.z, yv.z, tv.z, m, sc, r, w);
+        acc = acc + sweep_term(xv.w, yv.w, tv.w, m, sc, r, w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        part[((int64_t)b * C + c) * SWEEP_SLICES + s] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+__global__ __launch_bounds__(64) void sweep_sse_final_kernel(const double* __restrict__ part, double* __restrict__ out, int n) {
+    const int u = blockIdx.x * 64 + threadIdx.x;
+    if (u >= n) return;
+    double s = part[(int64_t)u * SWEEP_SLICES];
+    for (int p = 1; p < SWEEP_SLICES; ++p) s += part[(int64_t)u * SWEEP_SLICES + p];
+    out[u] = s;
+}
+
 // ------------------------------------------------------------------------------------------ ensemble metric sums
 // Per (sample b, variable v), over the grid with latitude weights (eval/metrics.py:39-134):
 //   out[b][v][0] = sum w (mean_n x - y)^2          (ensemble-mean RMSE)
@@ -1414,6 +1472,25 @@ extern "C" int swiftk_rmse_sums(const float* y, const float* t, int64_t t_batch_
     const dim3 grid((unsigned)grid_for((int64_t)B * H * W, 256, 64), (unsigned)C);
     hipLaunchKernelGGL(rmse_sums_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), y, t, t_batch_stride, w_lat, sq, B,
                        C, H, W);
+    SWIFTK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int swiftk_sweep_sse(const float* xstd, int64_t x_batch_stride, const float* y, const float* t, const float* mx,
+                                const float* sx, const float* st, const double* w_lat, double* out, double* scratch, int B, int C,
+                                int H, int W, void* stream) {
+    if (!xstd || !y || !t || !mx || !sx || !st || !w_lat || !out || !scratch || B <= 0 || C <= 0 || H <= 0 || W <= 0)
+        return SWIFTK_EINVAL;
+    if (x_batch_stride < (int64_t)C * H * W) return SWIFTK_EINVAL;  // the first C channels of every sample are read
+    if (W % 4 || B > 65535 || C > 65535 || (int64_t)H * W > INT32_MAX) return SWIFTK_ESHAPE;
+    if ((((uintptr_t)xstd | (uintptr_t)y | (uintptr_t)t) & 15) || (x_batch_stride & 3) ||
+        (((uintptr_t)w_lat | (uintptr_t)out | (uintptr_t)scratch) & 7) || (((uintptr_t)mx | (uintptr_t)sx | (uintptr_t)st) & 3))
+        return SWIFTK_EALIGN;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(sweep_sse_part_kernel, dim3(SWEEP_SLICES, (unsigned)C, (unsigned)B), dim3(256), 0, s, xstd, x_batch_stride, y,
+                       t, mx, sx, st, w_lat, scratch, C, H, W);
+    SWIFTK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sweep_sse_final_kernel, dim3((unsigned)((B * C + 63) / 64)), dim3(64), 0, s, scratch, out, B * C);
     SWIFTK_CHECK_LAUNCH();
     return 0;
 }

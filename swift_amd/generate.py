@@ -36,14 +36,24 @@ from . import dist
 from .config import Cfg, instantiate, load_saved
 from .rollout import RolloutEngine, unit_seed
 
-parser = argparse.ArgumentParser()
-parser.add_argument("--input", type=str, required=True, help="Input directory")
-parser.add_argument("--checkpoint", type=str, default=None, help="Checkpoint name (default: latest)")
+# the flags every CLI that loads a run shares (eval/sampler.py builds its parser on them too)
+common_parser = argparse.ArgumentParser(add_help=False)
+common_parser.add_argument("--input", type=str, required=True, help="Input directory")
+common_parser.add_argument("--checkpoint", type=str, default=None, help="Checkpoint name (default: latest)")
+common_parser.add_argument("--samples", type=int, default=-1, help="Number of samples use")
+common_parser.add_argument("--interval", type=int, default=6, choices=[6, 12, 24], help="Interval in hours")
+# additive
+common_parser.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16", "bf16x3"],
+                           help="compute engine: f32 = exact fp32 MFMA (the reference's arithmetic, factory.py:11); bf16x3 = fp32-grade "
+                                "(<= 1e-4 of the reference) from split-bf16 MFMA products, about twice as fast; bf16 = throughput engine")
+common_parser.add_argument("--synthetic", action="store_true", help="random-init weights + synthetic data (no run dir needed)")
+common_parser.add_argument("--gpus", type=int, default=None, help="start this many ranks (one per GPU) when not launched by torchrun/mpiexec")
+DENOISE_DTYPES = {"bf16": torch.bfloat16, "f32": torch.float32, "bf16x3": "bf16x3"}  # --dtype -> sampler_factory's denoise_dtype
+
+parser = argparse.ArgumentParser(parents=[common_parser])
 parser.add_argument("--members", type=int, default=1, help="Number of ensemble members")
 parser.add_argument("--steps", type=int, default=8, help="Number of prediction steps")
 parser.add_argument("--batch", type=int, default=32, help="(member, IC) units per device batch")
-parser.add_argument("--samples", type=int, default=-1, help="Number of samples use")
-parser.add_argument("--interval", type=int, default=6, choices=[6, 12, 24], help="Interval in hours")
 parser.add_argument("--dump", type=str, default=None, choices=["zarr", "numpy", "none"],
                     help="Output format (default: zarr, the reference's default, for a one-rank job; with more than one rank the "
                          "default is 'none' + --metrics -- the ensemble metrics, reduced on the devices, and no raw trajectories: one "
@@ -54,12 +64,7 @@ parser.add_argument("--solver", type=str, default=None, choices=["scm", "2s", "d
                     help="default: edm for an EDMPrecond run (settings from its saved solver config), else scm")
 parser.add_argument("--num-steps", type=int, default=None, help="solver steps per forecast step (default: 1; an EDM run's "
                     "saved solver.num_steps)")
-parser.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16", "bf16x3"],
-                    help="compute engine: f32 = exact fp32 MFMA (the reference's arithmetic, factory.py:11); bf16x3 = fp32-grade "
-                         "(<= 1e-4 of the reference) from split-bf16 MFMA products, about twice as fast; bf16 = throughput engine")
-parser.add_argument("--synthetic", action="store_true", help="random-init weights + synthetic data (no run dir needed)")
 parser.add_argument("--metrics", action="store_true", help="ensemble metrics vs the dataset's fields -> evaluation_metrics.json")
-parser.add_argument("--gpus", type=int, default=None, help="start this many ranks (one per GPU) when not launched by torchrun/mpiexec")
 
 
 def get_ckpt_num(fpath: str) -> int:
@@ -347,22 +352,16 @@ def collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, de
     return res
 
 
-def main(args):
+def load_cfg(args) -> Cfg:
+    """The run's saved composed config (generate.py:161), or the synthetic one when ``--synthetic`` names no run directory."""
     if args.synthetic and not os.path.exists(os.path.join(args.input, ".hydra", "config.yaml")):
-        cfg = synthetic_cfg()
-    else:
-        cfg = load_saved(os.path.join(args.input, ".hydra", "config.yaml"))
-    solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
-    dist.setup_torch(backend=cfg.system.torch.backend)
-    np.random.seed(cfg.seed % (1 << 31))
-    torch.manual_seed(np.random.randint(1 << 31))
-    device = dist.get_torch_device()
+        return synthetic_cfg()
+    return load_saved(os.path.join(args.input, ".hydra", "config.yaml"))
 
-    dist.log0("Loading dataset...")
-    dataset = instantiate(cfg.data.dataset, split="test", _convert_="object")
-    indices = select_indices(len(dataset), args.samples, args.steps, args.interval)
 
-    dist.log0("Constructing network...")
+def build_net(cfg, dataset, args, device):
+    """(net on the device in eval mode, checkpoint basename): the run's precond + model with the checkpoint's ``"ema"`` weights
+    (generate.py:200-226; ``--synthetic``: seeded random-init weights), loaded by rank 0 and broadcast to the others."""
     net = instantiate(cfg.precond, model_config=cfg.model, img_resolution=dataset.img_resolution,
                       img_channels=dataset.n_target_channels, condition_channels=dataset.n_condition_channels,
                       sigma_max=float("inf"), _recursive_=False, _convert_="object")
@@ -391,6 +390,23 @@ def main(args):
     if dist.collectives_active():  # one-time weight broadcast over RCCL / xGMI
         for p in net.parameters():
             tdist.broadcast(p.data, src=0)
+    return net, ckpt_basename
+
+
+def main(args):
+    cfg = load_cfg(args)
+    solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
+    dist.setup_torch(backend=cfg.system.torch.backend)
+    np.random.seed(cfg.seed % (1 << 31))
+    torch.manual_seed(np.random.randint(1 << 31))
+    device = dist.get_torch_device()
+
+    dist.log0("Loading dataset...")
+    dataset = instantiate(cfg.data.dataset, split="test", _convert_="object")
+    indices = select_indices(len(dataset), args.samples, args.steps, args.interval)
+
+    dist.log0("Constructing network...")
+    net, ckpt_basename = build_net(cfg, dataset, args, device)
 
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
@@ -414,7 +430,7 @@ def main(args):
         dist.run_on_rank0(create_empty_zarr, ofile, dataset, indices, args.members, args.steps, args.interval)
 
     engine = RolloutEngine(net, dataset, interval=args.interval, solver=solver,
-                           denoise_dtype={"bf16": torch.bfloat16, "f32": torch.float32, "bf16x3": "bf16x3"}[args.dtype],
+                           denoise_dtype=DENOISE_DTYPES[args.dtype],
                            **solver_kwargs)
     dist.log0("Rolling out samples...")
     t0 = time.time()

@@ -372,6 +372,26 @@ def zeros_acc(*shape, device) -> torch.Tensor:
     return zero_acc_(torch.empty(*shape, dtype=torch.float32, device=device))
 
 
+def sweep_sse(x: torch.Tensor, y: torch.Tensor, t: torch.Tensor, mx, sx, st, w_lat: torch.Tensor,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, C] fp64 latitude-weighted squared errors of the forecasts x[:, :C] + y against x[:, :C] + t in physical units
+    (``swiftk_sweep_sse``: the reference's fp32 arithmetic per element, fp64 sums in a fixed order -- a sample's row does not
+    depend on B or its batch slot).  x [B, >=C, H, W] standardised condition, y / t [B, C, H, W] standardised residuals,
+    mx / sx / st [C] fp32, w_lat [H] fp64."""
+    _dev(x, y, t, mx, sx, st, w_lat, out)
+    B, C, H, W = y.shape
+    assert x.dtype == y.dtype == t.dtype == torch.float32 and w_lat.dtype == torch.float64 and w_lat.numel() == H
+    assert y.is_contiguous() and t.is_contiguous() and t.shape == y.shape and x.shape[0] == B and x.shape[1] >= C
+    assert x.shape[2:] == y.shape[2:] and x[0].is_contiguous() and all(v.dtype == torch.float32 and v.numel() == C for v in (mx, sx, st))
+    if out is None:
+        out = torch.empty(B, C, dtype=torch.float64, device=y.device)
+    assert out.shape == (B, C) and out.dtype == torch.float64 and out.is_contiguous()
+    scratch = torch.empty(B, C, _lib.SWEEP_SLICES, dtype=torch.float64, device=y.device)
+    check(lib().swiftk_sweep_sse(x.data_ptr(), x.stride(0), y.data_ptr(), t.data_ptr(), mx.data_ptr(), sx.data_ptr(), st.data_ptr(),
+                                 w_lat.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, C, H, W, _stream()), "swiftk_sweep_sse")
+    return out
+
+
 def unit_checksum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp64 sum of every unit of x [B, ...] fp32 in a fixed order (bit-stable across ranks and batch slots) -> [B] fp64."""
     _dev(x, out)
