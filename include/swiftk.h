@@ -624,6 +624,28 @@ int swiftk_cast_pad(const float* src, int64_t lds, void* dst, int64_t ldd, int64
 int swiftk_cast_pad_t(const float* W, int64_t ldw, int64_t rows, int64_t cols, void* out, int64_t ldo, void* out_t, int64_t ldt,
                       int64_t interleave, void* stream);
 
+/* swiftk_cast_pad_t without the interleave and with the head-lane map of SWIFTK_PAD_HEADS on one axis: the two bf16 operands of a
+ * to_qkv / wo weight whose heads occupy hdp >= hd lanes on the device, straight from the fp32 parameter.  Along the lane axis the
+ * parameter has blocks * hd entries (blocks = 3 * heads for to_qkv's rows, heads for wo's columns); output index b * hdp + j takes
+ * parameter index b * hd + j for j < hd and is zero for hd <= j < hdp.
+ *   axis 0 (to_qkv): rows == blocks * hd;  out [blocks * hdp, ldo], out_t [cols, ldt], ldo >= cols, ldt >= blocks * hdp
+ *   axis 1 (wo):     cols == blocks * hd;  out [rows, ldo], out_t [blocks * hdp, ldt], ldo >= blocks * hdp, ldt >= rows
+ * Every element of both outputs is written exactly once (zero lanes and row paddings included); one rounding, to nearest even.
+ * Refused before any launch: a null pointer, a non-positive rows / cols / blocks / hd, hdp < hd, ldw < cols, an axis other than 0 / 1,
+ * ldo or ldt smaller than the lane-shaped extent above (SWIFTK_EINVAL); the lane axis not equal to blocks * hd, any extent or leading
+ * dimension above 2^30, more than 65535 row tiles of 64 (SWIFTK_ESHAPE; checked before ldo / ldt). */
+int swiftk_cast_pad_t_lanes(const float* W, int64_t ldw, int64_t rows, int64_t cols, void* out, int64_t ldo, void* out_t, int64_t ldt,
+                            int axis, int64_t blocks, int64_t hd, int64_t hdp, void* stream);
+
+/* Adjoint of that lane map on an fp32 weight gradient: G [rows, cols] (the parameter's shape, row stride ldg) += the valid lanes of the
+ * lane-shaped g (row stride ldl): G[r][c] += g[map(r)][c] for axis 0, g[r][map(c)] for axis 1, map(b * hd + j) = b * hdp + j.  One
+ * fp32 addition per element, no atomics; g's pad lanes are not read.
+ * Refused before any launch: a null pointer, a non-positive rows / cols / blocks / hd, hdp < hd, ldg < cols, an axis other than 0 / 1,
+ * ldl smaller than g's row (blocks * hdp for axis 1, cols for axis 0) (SWIFTK_EINVAL); the lane axis not equal to blocks * hd, an
+ * extent above 2^30 (SWIFTK_ESHAPE; checked before ldl). */
+int swiftk_lanes_grad_add(float* G, int64_t ldg, const float* g, int64_t ldl, int64_t rows, int64_t cols, int axis, int64_t blocks,
+                          int64_t hd, int64_t hdp, void* stream);
+
 /*
  * to_qkv + cosine norm + shifted-window attention of one layer in one kernel (bf16; head_dim 80 / 88 / 96 = the 468 M variant,
  * Swift-B, the 664 M variant of configs/experiment/era5-swinv2-1.4-scm.yaml:21-36; 16 x 16 windows; K >= 128): the q / k / v

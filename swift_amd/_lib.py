@@ -122,6 +122,8 @@ _SIGS = {
     "swiftk_modnorm_residual_pair_slabs_bf16": ([_p, _l, _l, _p, _l, _p, _l, _i, _p, _p, _p, _l, _l, _i, _l, _f, _p], _i),
     "swiftk_embed_bwd_sums": ([_p, _l, _p, _p, _p, _l, _l, _i, _l, _p], _i),
     "swiftk_cast_pad_t": ([_p, _l, _l, _l, _p, _l, _p, _l, _l, _p], _i),
+    "swiftk_cast_pad_t_lanes": ([_p, _l, _l, _l, _p, _l, _p, _l, _i, _l, _l, _l, _p], _i),
+    "swiftk_lanes_grad_add": ([_p, _l, _p, _l, _l, _l, _i, _l, _l, _l, _p], _i),
     "swiftk_gemm_modnorm_residual_pair": ([_p, _l, _p, _l, _l, _p, _l, _p, _l, _p, _p, _p, _l, _l, _i, _l, _f, _i, _p], _i),
     "swiftk_gemm_jvp": ([_p, _l, _p, _l, _p, _l, _l, _l, _l, _i, _p, _p, _i, _p, _l, _p], _i),
     "swiftk_ensemble_sums": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),

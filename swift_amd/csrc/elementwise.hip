@@ -1507,6 +1507,115 @@ extern "C" int swiftk_cast_pad_t(const float* W, int64_t ldw, int64_t rows, int6
     return 0;
 }
 
+// swiftk_cast_pad_t without the interleave, with the head-lane map on one axis (zero-padded head lanes): along that axis output index
+// b * hdp + j reads parameter index b * hd + j for j < hd and is zero for hd <= j < hdp.  Tiles are 64 x 64 of the OUTPUT (lane-shaped)
+// index space; both stores walk consecutive addresses and write every element of both buffers once, the zero lanes and the row paddings
+// included.  rl / cl: the lane-shaped extents.
+__device__ __forceinline__ int lane_src(int p, int hd, int hdp) {  // parameter index of lane-shaped index p, -1 on a pad lane
+    const int b = p / hdp, j = p - b * hdp;
+    return j < hd ? b * hd + j : -1;
+}
+
+__global__ __launch_bounds__(256) void cast_pad_t_lanes_kernel(const float* __restrict__ W, int64_t ldw, int rl, int cl,
+                                                               bf16_t* __restrict__ out, int64_t ldo, bf16_t* __restrict__ out_t,
+                                                               int64_t ldt, int axis, int hd, int hdp) {
+    __shared__ float tile[64][65];
+    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int cp = c0 + tx;
+    const int c = cp >= cl ? -1 : (axis == 1 ? lane_src(cp, hd, hdp) : cp);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int rp = r0 + ty + 4 * k;
+        float v = 0.f;
+        if (rp < rl && c >= 0) {
+            const int r = axis == 0 ? lane_src(rp, hd, hdp) : rp;
+            if (r >= 0) v = W[(int64_t)r * ldw + c];
+        }
+        tile[ty + 4 * k][tx] = v;
+        if (rp < rl && cp < ldo) out[(int64_t)rp * ldo + cp] = f2bf(v);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int ct = c0 + ty + 4 * k, rp = r0 + tx;
+        if (ct < cl && rp < ldt) out_t[(int64_t)ct * ldt + rp] = f2bf(tile[tx][ty + 4 * k]);
+    }
+}
+
+extern "C" int swiftk_cast_pad_t_lanes(const float* W, int64_t ldw, int64_t rows, int64_t cols, void* out, int64_t ldo, void* out_t,
+                                       int64_t ldt, int axis, int64_t blocks, int64_t hd, int64_t hdp, void* stream) {
+    if (!W || !out || !out_t || rows <= 0 || cols <= 0 || blocks <= 0 || hd <= 0 || hdp < hd || ldw < cols) return SWIFTK_EINVAL;
+    if (axis != 0 && axis != 1) return SWIFTK_EINVAL;
+    if (rows > (1 << 30) || cols > (1 << 30) || ldo > (1 << 30) || ldt > (1 << 30) || blocks > (1 << 30) || hdp > (1 << 30) ||
+        blocks * hdp > (1 << 30))
+        return SWIFTK_ESHAPE;
+    if ((axis == 0 ? rows : cols) != blocks * hd) return SWIFTK_ESHAPE;
+    const int64_t rl = axis == 0 ? blocks * hdp : rows, cl = axis == 1 ? blocks * hdp : cols;  // lane-shaped extents
+    if (ldo < cl || ldt < rl) return SWIFTK_EINVAL;
+    const int64_t rmax = rl > ldt ? rl : ldt, cmax = cl > ldo ? cl : ldo;
+    const dim3 grid((unsigned)((cmax + 63) / 64), (unsigned)((rmax + 63) / 64));
+    if (grid.y > 65535) return SWIFTK_ESHAPE;
+    hipLaunchKernelGGL(cast_pad_t_lanes_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), W, ldw, (int)rl, (int)cl,
+                       static_cast<bf16_t*>(out), ldo, static_cast<bf16_t*>(out_t), ldt, axis, (int)hd, (int)hdp);
+    SWIFTK_CHECK_LAUNCH();
+    return 0;
+}
+
+// Adjoint of the lane map on a weight gradient: G[r][c] += g[map(r)][c] (axis 0) or g[r][map(c)] (axis 1), map(b * hd + j) = b * hdp + j.
+// One thread per V consecutive columns of G (V = 4, 2 or 1: the widest that keeps a vector inside one head's valid lanes and aligned).
+template <int V>
+__global__ __launch_bounds__(256) void lanes_grad_add_kernel(float* __restrict__ G, int64_t ldg, const float* __restrict__ g, int64_t ldl,
+                                                             int cols, int64_t total, int axis, int hd, int hdp) {
+    const int cv = cols / V;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / cv), c = (int)(i - (int64_t)r * cv) * V;
+        int rs = r, cs = c;
+        if (axis == 0) rs = r / hd * hdp + r % hd;
+        else cs = c / hd * hdp + c % hd;
+        float* pg = G + (int64_t)r * ldg + c;
+        const float* ps = g + (int64_t)rs * ldl + cs;
+        if constexpr (V == 4) {
+            float4 a = *reinterpret_cast<float4*>(pg);
+            const float4 b = *reinterpret_cast<const float4*>(ps);
+            a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+            *reinterpret_cast<float4*>(pg) = a;
+        } else if constexpr (V == 2) {
+            float2 a = *reinterpret_cast<float2*>(pg);
+            const float2 b = *reinterpret_cast<const float2*>(ps);
+            a.x += b.x; a.y += b.y;
+            *reinterpret_cast<float2*>(pg) = a;
+        } else {
+            *pg += *ps;
+        }
+    }
+}
+
+extern "C" int swiftk_lanes_grad_add(float* G, int64_t ldg, const float* g, int64_t ldl, int64_t rows, int64_t cols, int axis,
+                                     int64_t blocks, int64_t hd, int64_t hdp, void* stream) {
+    if (!G || !g || rows <= 0 || cols <= 0 || blocks <= 0 || hd <= 0 || hdp < hd || ldg < cols) return SWIFTK_EINVAL;
+    if (axis != 0 && axis != 1) return SWIFTK_EINVAL;
+    if (rows > (1 << 30) || cols > (1 << 30) || blocks > (1 << 30) || hdp > (1 << 30) || blocks * hdp > (1 << 30)) return SWIFTK_ESHAPE;
+    if ((axis == 0 ? rows : cols) != blocks * hd) return SWIFTK_ESHAPE;
+    if (ldl < (axis == 1 ? blocks * hdp : cols)) return SWIFTK_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const auto fits = [&](int64_t v) {  // vectors of v floats: whole ones per row, never across a lane boundary, aligned on both sides
+        return cols % v == 0 && ldg % v == 0 && ldl % v == 0 && (axis == 0 || (hd % v == 0 && hdp % v == 0)) &&
+               !((uintptr_t)G & (4 * v - 1)) && !((uintptr_t)g & (4 * v - 1));
+    };
+    const int V = fits(4) ? 4 : (fits(2) ? 2 : 1);
+    const int64_t total = rows * (cols / V);
+    const dim3 grid(grid_for(total));
+    if (V == 4)
+        hipLaunchKernelGGL(lanes_grad_add_kernel<4>, grid, dim3(256), 0, st, G, ldg, g, ldl, (int)cols, total, axis, (int)hd, (int)hdp);
+    else if (V == 2)
+        hipLaunchKernelGGL(lanes_grad_add_kernel<2>, grid, dim3(256), 0, st, G, ldg, g, ldl, (int)cols, total, axis, (int)hd, (int)hdp);
+    else
+        hipLaunchKernelGGL(lanes_grad_add_kernel<1>, grid, dim3(256), 0, st, G, ldg, g, ldl, (int)cols, total, axis, (int)hd, (int)hdp);
+    SWIFTK_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int swiftk_split3(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t cols, int order,
                              void* stream) {
     if (!src || !dst || rows <= 0 || cols <= 0 || lds < cols || ldd < 3 * cols || (order != 0 && order != 1)) return SWIFTK_EINVAL;

@@ -37,12 +37,19 @@ def check_head_dim(module, dtype) -> None:
         raise SwiftkError(f"head_dim = dim / heads = {d} / {heads} = {d / max(heads, 1):g} is not supported by the gfx950 kernels: "
                           f"head_dim must be one of {', '.join(map(str, HEAD_DIMS))} (or 64 on the exact-fp32 attention); "
                           f"choose model.heads so that dim / heads is one of them. SWIFTK_PAD_HEADS=1 runs a width of up to "
-                          f"{HEAD_DIMS[-1]} on zero-padded head lanes (forward and training engines)")
+                          f"{HEAD_DIMS[-1]} on zero-padded head lanes (forward and training engines; SWIFTK_PAD_HEADS=2: the "
+                          f"tangent engine of sCM and distillation as well)")
 
 
 def pad_heads_enabled() -> bool:
     """The SWIFTK_PAD_HEADS switch, read when an engine is built (README, environment switches)."""
     return os.environ.get("SWIFTK_PAD_HEADS", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+def pad_heads_tangent_enabled() -> bool:
+    """Level 2 of the switch: the tangent engine (sCM pre-training, distillation) runs padded lanes too.  Levels 0 and 1 keep its
+    refusal of a width other than 80 / 88 / 96."""
+    return os.environ.get("SWIFTK_PAD_HEADS", "0").strip() == "2"
 
 
 def head_lanes(dim: int, heads: int, dtype):

@@ -24,6 +24,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
+from .engine import HEAD_DIMS, head_lanes, pack_qkv_lanes, pack_wo_lanes, pad_heads_tangent_enabled
 from .graphs import GraphCache
 from ._lib import EPI_BIAS_POS, EPI_NONE, EPI_QKNORM_JVP, EPI_SWIGLU_JVP, SwiftkError, check, lib
 
@@ -47,9 +48,16 @@ def _gemm(a, w, out, epi=EPI_NONE, ep0=None, ep1=None, pos_rows=0, k=None):
 class SwinJvpEngine:
     def __init__(self, module, dtype: torch.dtype = torch.bfloat16):
         self.m = module
-        self.hd = module.dim // module.heads
+        # hd0: the model's head width; hd: the width its heads occupy on the device.  SWIFTK_PAD_HEADS=2 runs a narrower head on zero
+        # lanes up to 80 / 88 / 96 as the training engine does (engine.head_lanes; the tangent kernels have no 64 even in fp32, so the
+        # bf16 widths hold for both operand types); every other level refuses it
+        self.hd0 = self.hd = module.dim // module.heads
+        if (pad_heads_tangent_enabled() and self.hd0 not in HEAD_DIMS and module.dim % module.heads == 0
+                and 1 <= self.hd0 <= HEAD_DIMS[-1]):
+            self.hd0, self.hd = head_lanes(module.dim, module.heads, torch.bfloat16)
         if self.hd not in (80, 88, 96):
             raise SwiftkError("the tangent kernels are built for head_dim 80 / 88 / 96")
+        self.inner = module.heads * self.hd  # columns per q / k / v and per attention-output row (= dim unless lanes are padded)
         self.dt = dtype
         self._stamp = None
         self._buf = {}            # persistent operand copies (fixed addresses for the captured launch sequence)
@@ -65,7 +73,7 @@ class SwinJvpEngine:
         te_key = None
         if te is not None and dt == torch.bfloat16:
             te.refresh()
-            te_key = (id(te),) + tuple(l[k].data_ptr() for l in te.L for k in ("qkv", "wo", "w1", "w2"))
+            te_key = (id(te), te.hd, te.inner, te.katt) + tuple(l[k].data_ptr() for l in te.L for k in ("qkv", "wo", "w1", "w2"))
         if stamp == self._stamp and te_key == getattr(self, "_te_key", None):
             return
         if te_key != getattr(self, "_te_key", None) and getattr(self, "_share", False):
@@ -80,6 +88,8 @@ class SwinJvpEngine:
         mlp_e = self.mlp_e = (mlp + 7) // 8 * 8  # odd MLP widths (dim 1280 -> 3413): zero (gate, up) row pairs, as in SwinEngine
         self.kd, self.kmlp = ops.k_pad(dt, d), ops.k_pad(dt, mlp_e)
         self.kpe = ops.k_pad(dt, m.in_channels * m.patch_size[0] * m.patch_size[1])
+        heads, hd0, hd, inner = m.heads, self.hd0, self.hd, self.inner
+        self.katt = ops.k_pad(dt, inner)  # wo's K (= kd unless lanes are padded)
         dev0 = m.pos_embed.device
         ctr = [0]
 
@@ -106,6 +116,7 @@ class SwinJvpEngine:
         share = te is not None and dt == torch.bfloat16 and getattr(te, "mlp_e", None) == mlp_e
         if share:
             share = te.kd == self.kd and te.kmlp == self.kmlp and len(te.L) == len(m.transformer.layers)
+            share = share and (te.hd, te.inner, te.katt) == (hd, inner, self.katt)
         if getattr(self, "_share", share) != share:
             self.graphs.invalidate()  # (captured sequences hold the other set of operand addresses)
         self._share = share
@@ -117,6 +128,20 @@ class SwinJvpEngine:
                 torch.cat(ts, 0, out=self._buf[name])
             return self._buf[name]
 
+        def cast_lanes(w, k, axis, blocks):
+            """``cast`` of a to_qkv / wo weight onto padded head lanes: bf16 operands in one pass over the parameter
+            (``swiftk_cast_pad_t_lanes``; its transposed output goes to a scratch buffer), fp32 ones packed on the host side."""
+            w = w.detach()
+            if dt != torch.bfloat16:
+                return cast(pack_qkv_lanes(w, heads, hd0, hd) if axis == 0 else pack_wo_lanes(w, heads, hd0, hd), k)
+            ctr[0] += 1
+            if w.dtype != torch.float32 or w.stride(1) != 1:
+                w = w.float().contiguous()
+            rl, cl = (blocks * hd, w.shape[1]) if axis == 0 else (w.shape[0], blocks * hd)
+            scratch = torch.empty(cl, rl, dtype=dt, device=dev0)
+            return keep(f"c{ctr[0]}", lambda: torch.empty(rl, k, dtype=dt, device=dev0),
+                        lambda b: ops.cast_pad_t_lanes(w, b, scratch, axis, blocks, hd0, hd))
+
         self.L = []
         mods_w, mods_b = [], []
         for li, (att, ff) in enumerate(m.transformer.layers):
@@ -126,8 +151,11 @@ class SwinJvpEngine:
                 w1i = ff.w1.weight.detach().view(2, mlp, d).permute(1, 0, 2).reshape(2 * mlp, d)  # (gate_j, up_j) interleaved
                 if mlp_e != mlp:
                     w1i = torch.cat([w1i, w1i.new_zeros(2 * (mlp_e - mlp), d)], 0)
-                ops4 = dict(qkv=cast(att.to_qkv.weight, self.kd), wo=cast(att.wo.weight, self.kd), w1=cast(w1i, self.kd),
-                            w2=cast(ff.w2.weight, self.kmlp))
+                if hd != hd0:  # padded head lanes: zero rows of to_qkv / zero columns of wo
+                    qkv, wo = cast_lanes(att.to_qkv.weight, self.kd, 0, 3 * heads), cast_lanes(att.wo.weight, self.katt, 1, heads)
+                else:
+                    qkv, wo = cast(att.to_qkv.weight, self.kd), cast(att.wo.weight, self.kd)
+                ops4 = dict(qkv=qkv, wo=wo, w1=cast(w1i, self.kd), w2=cast(ff.w2.weight, self.kmlp))
             self.L.append(dict(**ops4, scale=att.scale.detach().reshape(-1).float().contiguous(),
                                g1=att.norm.norm.weight.detach().float().contiguous(),
                                b1=att.norm.norm.bias.detach().float().contiguous(),
@@ -177,7 +205,7 @@ class SwinJvpEngine:
         tc = ops.dtype_code(T)
         dev = srcs[0].device
         B = srcs[0].shape[0]
-        d, heads, mlp = m.dim, m.heads, self.mlp_e
+        d, heads, mlp, inner = m.dim, m.heads, self.mlp_e, self.inner
         gh, gw = m.grid_size
         ntok = gh * gw
         M = B * ntok
@@ -240,7 +268,7 @@ class SwinJvpEngine:
                  and mlp % 8 == 0 and not os.environ.get("SWIFTK_JVP_UNFUSED"))
         kk = d  # (d = 16.5 k-tiles: the kernel skips the zero half of the last one)
         # one buffer set reused by every layer -- or, when the primal rows are kept for a backward pass, one set per layer
-        shared = None if save else dict(QKV=torch.empty(2 * M, 3 * d, dtype=T, device=dev), ATT=operand(self.kd, d),
+        shared = None if save else dict(QKV=torch.empty(2 * M, 3 * inner, dtype=T, device=dev), ATT=operand(self.katt, inner),
                                         Y=torch.empty(2 * M, d, dtype=T, device=dev),
                                         H=None if fused else torch.empty(2 * M, 2 * mlp, dtype=T, device=dev), HM=operand(self.kmlp, mlp))
 
@@ -263,22 +291,22 @@ class SwinJvpEngine:
         for i in range(len(self.L)):
             W = self.L[i]
             sh = tuple(m.shift_size) if (do_shift and i % 2) else (0, 0)
-            QKV = shared["QKV"] if shared else torch.empty(2 * M, 3 * d, dtype=T, device=dev)
+            QKV = shared["QKV"] if shared else torch.empty(2 * M, 3 * inner, dtype=T, device=dev)
             rn = torch.empty(M, 3 * heads, dtype=torch.float32, device=dev) if save else None
             if fused:  # to_qkv with the cosine-attention prologue and its tangent in the GEMM's epilogue (paired rows)
-                check(L.swiftk_gemm_jvp(XT_in.data_ptr(), XT_in.stride(0), W["qkv"].data_ptr(), W["qkv"].stride(0), QKV.data_ptr(), 3 * d,
-                                        M, 3 * d, kk, EPI_QKNORM_JVP, W["scale"].data_ptr(),
+                check(L.swiftk_gemm_jvp(XT_in.data_ptr(), XT_in.stride(0), W["qkv"].data_ptr(), W["qkv"].stride(0), QKV.data_ptr(), 3 * inner,
+                                        M, 3 * inner, kk, EPI_QKNORM_JVP, W["scale"].data_ptr(),
                                         None if rn is None else rn.data_ptr(), self.hd, None, 0, _s()), "swiftk_gemm_jvp")
             else:
                 _gemm(XT_in, W["qkv"], QKV, k=d)
-                check(L.swiftk_qknorm_jvp(QKV.data_ptr(), QKV.data_ptr() + M * 3 * d * es, 3 * d, W["scale"].data_ptr(),
+                check(L.swiftk_qknorm_jvp(QKV.data_ptr(), QKV.data_ptr() + M * 3 * inner * es, 3 * inner, W["scale"].data_ptr(),
                                           None if rn is None else rn.data_ptr(), M, heads, self.hd, tc, _s()), "swiftk_qknorm_jvp")
-            ATT = shared["ATT"] if shared else operand(self.kd, d)
-            check(L.swiftk_window_attention_jvp(QKV.data_ptr(), QKV.data_ptr() + M * 3 * d * es, 3 * d, ATT.data_ptr(),
-                                                ATT.data_ptr() + M * self.kd * es, self.kd, B, gh, gw, heads, self.hd, sh[0], sh[1],
+            ATT = shared["ATT"] if shared else operand(self.katt, inner)
+            check(L.swiftk_window_attention_jvp(QKV.data_ptr(), QKV.data_ptr() + M * 3 * inner * es, 3 * inner, ATT.data_ptr(),
+                                                ATT.data_ptr() + M * self.katt * es, self.katt, B, gh, gw, heads, self.hd, sh[0], sh[1],
                                                 tc, _s()), "swiftk_window_attention_jvp")
             Y1 = shared["Y"] if shared else torch.empty(2 * M, d, dtype=T, device=dev)
-            _gemm(ATT, W["wo"], Y1, k=d)
+            _gemm(ATT, W["wo"], Y1, k=inner)
             XT_mid = XT_in if shared else operand(self.kd, d)
             modnorm(2 * i, W["g1"], W["b1"], Y1, XT_mid, XT_in)
             HM = shared["HM"] if shared else operand(self.kmlp, mlp)

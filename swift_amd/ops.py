@@ -66,6 +66,27 @@ def cast_pad_t(w: torch.Tensor, out: torch.Tensor, out_t: torch.Tensor, interlea
                                   out_t.stride(0), int(interleave), _stream()), "swiftk_cast_pad_t")
 
 
+def cast_pad_t_lanes(w: torch.Tensor, out: torch.Tensor, out_t: torch.Tensor, axis: int, blocks: int, hd: int, hdp: int) -> None:
+    """``cast_pad_t`` of a to_qkv (``axis`` 0, ``blocks`` = 3 * heads) or wo (``axis`` 1, ``blocks`` = heads) weight onto padded head
+    lanes: ``out`` / ``out_t`` are those of ``cast_pad_t(pack_*_lanes(w), ...)``, written in one pass over the parameter itself."""
+    _dev(w, out, out_t)
+    assert w.dtype == torch.float32 and w.dim() == 2 and w.stride(1) == 1 and out.dtype == out_t.dtype == torch.bfloat16
+    rl, cl = (blocks * hdp, w.shape[1]) if axis == 0 else (w.shape[0], blocks * hdp)
+    assert out.shape[0] == rl and out_t.shape[0] == cl and out.stride(1) == 1 and out_t.stride(1) == 1
+    check(lib().swiftk_cast_pad_t_lanes(w.data_ptr(), w.stride(0), w.shape[0], w.shape[1], out.data_ptr(), out.stride(0),
+                                        out_t.data_ptr(), out_t.stride(0), int(axis), int(blocks), int(hd), int(hdp), _stream()),
+          "swiftk_cast_pad_t_lanes")
+
+
+def lanes_grad_add(G: torch.Tensor, g: torch.Tensor, axis: int, blocks: int, hd: int, hdp: int) -> None:
+    """``G += unpack_*_lanes(g)``: the valid lanes of a lane-shaped fp32 weight gradient added into the parameter's gradient."""
+    _dev(G, g)
+    assert G.dtype == g.dtype == torch.float32 and G.dim() == g.dim() == 2 and G.stride(1) == 1 and g.stride(1) == 1
+    assert g.shape == ((blocks * hdp, G.shape[1]) if axis == 0 else (G.shape[0], blocks * hdp))
+    check(lib().swiftk_lanes_grad_add(G.data_ptr(), G.stride(0), g.data_ptr(), g.stride(0), G.shape[0], G.shape[1], int(axis),
+                                      int(blocks), int(hd), int(hdp), _stream()), "swiftk_lanes_grad_add")
+
+
 def split3(w: torch.Tensor, order: int, cols: Optional[int] = None) -> torch.Tensor:
     """fp32 [rows, c] -> bf16 [rows, k_pad(bf16, 3 * cols)]: the three-block (hi / lo) operand of the bf16x3 engine
     (``swiftk_split3``; order 0 = activations [hi | lo | hi], 1 = weights [hi | hi | lo]).  ``cols`` >= c: zero columns are

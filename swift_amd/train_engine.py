@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from ._lib import (ATTN_PRENORM, BF16, EPI_ACCUM, EPI_BIAS_POS, EPI_NONE, EPI_QKNORM, EPI_SWIGLU_BOTH, EPI_SWIGLU_BWD, F32, SwiftkError, check, lib)
-from .engine import head_lanes, pack_qkv_lanes, pack_wo_lanes, unpack_qkv_lanes, unpack_wo_lanes
+from .engine import head_lanes
 from .graphs import GraphCache
 
 _BF = torch.bfloat16
@@ -139,11 +139,27 @@ class SwinTrainEngine:
             return self._keep(f"f{ctr[0]}", lambda: torch.empty_like(t, memory_format=torch.contiguous_format),
                               lambda b: b.copy_(t))
 
+        def both_lanes(w, k, kt, axis, blocks):
+            """``both`` of a to_qkv / wo weight on padded head lanes: zero rows (axis 0) / zero columns (axis 1) per head appear on
+            the way through the same single pass (``swiftk_cast_pad_t_lanes``)."""
+            ctr[0] += 2
+            w = w.detach()
+            if w.dtype != torch.float32 or w.stride(1) != 1:
+                w = w.float().contiguous()
+            rl, cl = (blocks * hd, w.shape[1]) if axis == 0 else (w.shape[0], blocks * hd)
+            a = self._keep(f"c{ctr[0] - 1}", lambda: torch.empty(rl, k, dtype=_BF, device=dev0), lambda b: None)
+            b_ = self._keep(f"c{ctr[0]}", lambda: torch.empty(cl, kt, dtype=_BF, device=dev0), lambda b: None)
+            ops.cast_pad_t_lanes(w, a, b_, axis, blocks, hd0, hd)
+            return a, b_
+
         self.L = []
         for att, ff in m.transformer.layers:
-            # (padded head lanes: zero rows of to_qkv / zero columns of wo on the host side, then one pass each, as the MLP width below)
-            qkv, qkv_t = both(pack_qkv_lanes(att.to_qkv.weight.detach(), heads, hd0, hd), self.kd, self.kqkv)
-            wo, wo_t = both(pack_wo_lanes(att.wo.weight.detach(), heads, hd0, hd), self.katt, self.kd)
+            if hd != hd0:  # padded head lanes: zero rows of to_qkv / zero columns of wo
+                qkv, qkv_t = both_lanes(att.to_qkv.weight, self.kd, self.kqkv, 0, 3 * heads)
+                wo, wo_t = both_lanes(att.wo.weight, self.katt, self.kd, 1, heads)
+            else:
+                qkv, qkv_t = both(att.to_qkv.weight, self.kd, self.kqkv)
+                wo, wo_t = both(att.wo.weight, self.katt, self.kd)
             if mlp_e != mlp:  # (the padded MLP width of dim 1280: interleave and zero-extend on the host side, then one pass each)
                 w1i = ff.w1.weight.detach().view(2, mlp, d).permute(1, 0, 2).reshape(2 * mlp, d)
                 w1i = torch.cat([w1i, w1i.new_zeros(2 * (mlp_e - mlp), d)], 0)
@@ -438,7 +454,7 @@ class SwinTrainEngine:
                 self._wgrad(dy1, A["att"], d, d, G(att.wo.weight))
             else:
                 self._wgrad(dy1, A["att"], d, inner, gwo, accumulate=False)
-                G(att.wo.weight).add_(unpack_wo_lanes(gwo, heads, hd0, hd))
+                ops.lanes_grad_add(G(att.wo.weight), gwo, 1, heads, hd0, hd)
             # d(q | k | v) lands in the to_qkv data-gradient GEMM's operand buffer (row stride kqkv): the attention backward applies
             # the QK-norm backward to its accumulators on their way out (head_dim 88; elsewhere a second pass rewrites the q-hat / k-hat
             # vectors in place -- v's gradient is already final)
@@ -454,7 +470,7 @@ class SwinTrainEngine:
                 self._wgrad(dqkv, A["xT_in"], 3 * d, d, G(att.to_qkv.weight))
             else:
                 self._wgrad(dqkv, A["xT_in"], 3 * inner, d, gqkv, accumulate=False)
-                G(att.to_qkv.weight).add_(unpack_qkv_lanes(gqkv, heads, hd0, hd))
+                ops.lanes_grad_add(G(att.to_qkv.weight), gqkv, 0, 3 * heads, hd0, hd)
             if grads_final is not None:  # everything of layer i except its modulation Linears (those follow in _embed_bwd)
                 grads_final([p for n, p in m.transformer.layers[i].named_parameters() if "modulation" not in n])
         # ---- patch embedding: x0 = ape @ Wpe^T + b + pos

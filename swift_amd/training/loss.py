@@ -306,7 +306,10 @@ class SCMLoss(_LossBase):
         env = os.environ.get("SWIFTK_SCM_ONE_PASS")
         fits = _plan_once(self._plans, ("scm_one_pass", B, env), lambda: int(env != "0") if env is not None else
                           int(4.4 * eng.activation_bytes(B) <= _memory_budget(dev)), "one-pass sCM", dev)
-        one_pass = bool(jeng.dt == torch.bfloat16 and jeng.mlp_e == eng.mlp_e and fits)
+        # (activation_bytes counts the engine's own buffers: qkvh / att are inner- / katt-wide on padded head lanes, and the tangent
+        # pass saves them at the same widths -- its context is the training engine's only when both pad alike)
+        one_pass = bool(jeng.dt == torch.bfloat16 and jeng.mlp_e == eng.mlp_e and (jeng.hd, jeng.inner, jeng.katt) ==
+                        (eng.hd, eng.inner, eng.katt) and fits)
         self.last_one_pass = one_pass
         with torch.no_grad():
             if one_pass:
