@@ -51,115 +51,70 @@ constexpr int EPI_QKNORM_TILED = 4;  // internal: SWIFTK_EPI_QKNORM with the win
 constexpr int EPI_NONE_TAIL = 12;     // internal: SWIFTK_EPI_NONE with the LAST ROUND's tiles as two k-halves (swiftk_gemm_tail_split_bf16)
 constexpr int EPI_BIAS_POS_PAIR = 11;  // internal: SWIFTK_EPI_BIAS_POS leaving as the (bf16 hi, 8-bit lo) pair (swiftk_gemm_bias_pos_pair)
 
-// Build-time switches.  SWIFTK_GEMM_INSTR = 1 compiles the timing experiments (tuning key 3: ablation bits, s_memtime
-// timeline) into the persistent kernel -- `make variant EXTRA=-DSWIFTK_GEMM_INSTR=1`, never into libswiftk.so.
-#ifndef SWIFTK_GEMM_INSTR
-#define SWIFTK_GEMM_INSTR 0
-#endif
-#ifndef SWIFTK_X_VMCNT
-#define SWIFTK_X_VMCNT 1
-#endif
-#ifndef SWIFTK_X_PRIO
-#define SWIFTK_X_PRIO 1
-#endif
-#ifndef SWIFTK_X_PF2
-#define SWIFTK_X_PF2 1
-#endif
-// timing probe with WRONG results: read only every n-th W fragment from LDS (n = 2: 10 instead of 15 ds_read_b128 per 44 MFMAs,
-// the ratio a one-wave-per-SIMD 128 x 176 register tile would have) -- does the plateau move with LDS reads per MFMA?
-#ifndef SWIFTK_X_FEWREADS
-#define SWIFTK_X_FEWREADS 0
-#endif
-#ifndef SWIFTK_X_NOSILU
-#define SWIFTK_X_NOSILU 0
-#endif
-// patch embedding: 1 = tile rows walked sample-fastest so that a pos_embed block is shared by an XCD's whole window (TileIter).
-// Measured in round 6 (profiles/r06o_posperm_ab.txt): 2,161 us against 2,098 us per launch at 96 units in storage order -- the
-// epilogue does not wait for pos_embed's Infinity-Cache fetches; off
-#ifndef SWIFTK_X_POSPERM
-#define SWIFTK_X_POSPERM 0
-#endif
-// SWIGLU_BWD epilogue: R > 0 = a rolling window of R saved pre-activation chunks per lane (R loads in flight) instead of two groups of four.
-// Measured in round 6 (profiles/r06m_gemm_ab_bwdroll.txt): R = 8 +3.3 %, R = 10 +4.2 % SLOWER (bit-equal): the epilogue is not short of loads in flight
-#ifndef SWIFTK_X_BWDROLL
-#define SWIFTK_X_BWDROLL 0
-#endif
-// cache policy of the bf16 output tiles' 16-B stores: 0 = default, 1 = nt, 2 = sc1 (write-through, line not kept in the
-// XCD's L2), 3 = sc0 sc1.  The outputs are written once and never re-read by the kernel; a round of 32 tiles per XCD writes
-// 5.8 MB through a 4 MB L2 that should be holding the W panel the XCD re-reads every round.
-// SWIGLU_BWD: pull the tile's saved pre-activations (256 rows x 11 lines, 360 KB) into the XCD's L2 during the tile's last
-// k-tile (six 4-byte-per-lane LDS-DMA requests per wave into a scratch area), so the epilogue's 16-B reads -- two groups
-// of four in flight per lane, twelve groups per tile -- wait for L2 instead of HBM.  Measured 659 against 594 us per launch at
-// local batch 8 (profiles/r03p_gemm_ab_hpf.txt): off.
-#ifndef SWIFTK_X_HPF
-#define SWIFTK_X_HPF 0
-#endif
-#ifndef SWIFTK_X_STORE
-#define SWIFTK_X_STORE 0
-#endif
-// L2 look-ahead of the persistent kernel (k-tiles): in the second half of every k-tile (where no DMA piece is issued) each
-// wave requests one 4-byte LDS-DMA per lane from the 128-B lines its workgroup will stage SWIFTK_X_TOUCH + 1 k-tiles later;
-// the k-tile's closing wait leaves those two requests in flight (counted vmcnt), so their miss latency is never waited for.
-// non-temporal LDS-DMA for the activation operand (A/B experiment)
-#ifndef SWIFTK_X_ANT
-#define SWIFTK_X_ANT 0
-#endif
-#ifndef SWIFTK_X_TOUCH
-#define SWIFTK_X_TOUCH 0
-#endif
-// Ping-pong k-loop (cdna_hip_programming.md section 5, "8-phase" schedule, on this kernel's 256 x 352 geometry): a k-tile is
-// four phases (k-half x column half of the wave tile); in every phase a wave first requests the phase's fragments from LDS
+// Ping-pong k-loop (cdna_hip_programming.md section 5, "8-phase" schedule, on this kernel's 256 x 352 geometry; tuning key 20): a
+// k-tile is four phases (k-half x column half of the wave tile); in every phase a wave first requests the phase's fragments from LDS
 // and issues its share of the next stage's DMA pieces (MEM), then -- behind a workgroup barrier -- runs the phase's 20-24 MFMAs
 // back to back (COMPUTE), then a second barrier.  Waves 4-7 (the SIMD partners of waves 0-3) run one barrier behind, so on every
 // SIMD one wave is in COMPUTE while its partner is in MEM: fragment-read latency and DMA issue never sit between a wave's own
-// MFMAs.  1 = per-k-tile drain of the DMA (placed in the last MEM phase); 2 = counted: the W pieces of the second column
-// half stay in flight across the k-tile boundary and are waited for in the next k-tile's first MEM phase.
-#ifndef SWIFTK_X_PP
-#define SWIFTK_X_PP 1
-#endif
-#ifndef SWIFTK_X_PP_PRIO
-#define SWIFTK_X_PP_PRIO 1
-#endif
-// diagnostic build of the ping-pong loop (never in libswiftk.so): tuning key 3 bits 1 / 4 / 8 as in SWIFTK_GEMM_INSTR (no DMA, no
-// epilogue, every stage re-reads k-tile 0), bit 64 = s_memtime stamps of waves 0 and 4 of every 32nd workgroup around every
-// barrier of the workgroup's second tile, into the buffer passed as ep1 (EPI_NONE): [wg / 32][wave group][k-tile][16] uint64
+// MFMAs.  The W pieces of the second column half stay in flight across the k-tile boundary and are waited for in the next k-tile's
+// first MEM phase.
+//
+// The one build-time switch: a diagnostic build of the ping-pong loop (`make variant EXTRA=-DSWIFTK_PP_STAMP=1`, never in
+// libswiftk.so).  Tuning key 3 bits 1 / 4 / 8 = no DMA in the loop, no epilogue, every stage re-reads k-tile 0 (all give wrong
+// results); bit 64 = s_memtime stamps of waves 0 and 4 of every 32nd workgroup around every barrier of the workgroup's second tile,
+// into the buffer passed as ep1 (EPI_NONE): [wg / 32][wave group][k-tile][16] uint64
 #ifndef SWIFTK_PP_STAMP
 #define SWIFTK_PP_STAMP 0
 #endif
-// bf16 epilogue: request all of a 16-row slab's row chunks from LDS before the first store (1) or chunk by chunk (0)
-#ifndef SWIFTK_X_EPIBATCH
-#define SWIFTK_X_EPIBATCH 0
-#endif
 
+// The kernel argument.  Every field has its "off" value as default; make_args fills what every entry point sets.
 struct GemmArgs {
-    const char* A;
-    const char* W;
-    char* C;
-    int64_t lda_b, ldw_b;  // row strides in bytes
-    int64_t ldc;           // row stride of C in elements
-    int M, N, K;
-    const float* ep0;
-    const float* ep1;
-    int pos_rows;
-    int ntn;
-    int ni;   // W-side MFMA tiles per wave of the persistent kernel's geometry: 10 / 11 / 12 = 320 / 352 / 384 columns per tile
+    const char* A = nullptr;
+    const char* W = nullptr;
+    char* C = nullptr;
+    int64_t lda_b = 0, ldw_b = 0;  // row strides in bytes
+    int64_t ldc = 0;               // row stride of C in elements
+    int M = 0, N = 0, K = 0;
+    const float* ep0 = nullptr;
+    const float* ep1 = nullptr;
+    int pos_rows = 0;
+    int ntn = 0;
+    int ni = 11;  // W-side MFMA tiles per wave of the persistent kernel's geometry: 10 / 11 / 12 = 320 / 352 / 384 columns per tile
     int qk_only = 0;  // SWIFTK_EPI_QKNORM with fp32 operands: W rows / C columns are [q|k] pairs picked out of [q|k|v] triples (swiftk_gemm, pos_rows < 0)
-    int dbg;  // tuning experiments only: 1 = no DMA in the loop, 2 = no barrier (both give wrong results)
-    int khalf;         // the last k-tile holds data in its first half only (K = 16.5 tiles for d = 1056)
-    int touch;         // persistent kernel: L2 look-ahead requests on (aligned shapes only: M % 256 == 0, N % tile width == 0)
-    int stagger;       // persistent kernel: start-up delay step in 10-ns ticks (workgroup phase p waits p x stagger); 0 = off
-    int ksplit;        // persistent kernel: k-ranges per output tile (1 = plain)
-    int tail_from;     // EPI_NONE_TAIL: tiles >= tail_from (in the walk's tile order) run as two k-halves into slabs 0 / 1 (C + c_split)
-    int64_t c_split;   // elements between the fp32 slabs of consecutive splits
-    int64_t batch_a, batch_w, batch_c;  // one-tile-per-workgroup kernel only: byte steps of A / W / C per blockIdx.y (batched GEMM)
+    int dbg = 0;      // SWIFTK_PP_STAMP builds only (tuning key 3): 1 = no DMA in the loop, 4 = no epilogue, 8 = k-tile 0 re-read, 64 = stamps
+    int khalf = 0;    // the last k-tile holds data in its first half only (K = 16.5 tiles for d = 1056)
+    int reserved = 0;  // (unread; without it the compiler merges the kernels' scalar argument loads differently and every kernel changes)
+    int stagger = 0;    // persistent kernel: start-up delay step in 10-ns ticks (workgroup phase p waits p x stagger); 0 = off
+    int ksplit = 1;     // persistent kernel: k-ranges per output tile (1 = plain)
+    int tail_from = 0;  // EPI_NONE_TAIL: tiles >= tail_from (in the walk's tile order) run as two k-halves into slabs 0 / 1 (C + c_split)
+    int64_t c_split = 0;  // elements between the fp32 slabs of consecutive splits
+    int64_t batch_a = 0, batch_w = 0, batch_c = 0;  // one-tile-per-workgroup kernel only: byte steps of A / W / C per blockIdx.y (batched GEMM)
     // QKNORM only: window-tiled output [sample][window][head][q|k|v][256][88] (t_gw = 0: plain row-major C)
-    int t_gh, t_gw, t_sh, t_sw, t_heads;
+    int t_gh = 0, t_gw = 0, t_sh = 0, t_sw = 0, t_heads = 0;
     // fp32 operands, persistent kernel: two-level accumulation.  Every `kchunk` k-tiles a workgroup parks its accumulators in
     // its private slab of `kscr` (lane-major float4s: blockIdx.x, wave, (i, j), lane) and restarts from zero; a tile's last
     // k-tile adds the parked sum back before the epilogue.  0 = one chain over the whole K range.
-    float* kscr;
-    int kchunk;
+    float* kscr = nullptr;
+    int kchunk = 0;
 };
+
+// operands, byte strides and shape of one product; `ni` picks the tile width (32 ni columns) that `ntn` counts
+inline GemmArgs make_args(const void* A, int64_t lda_b, const void* W, int64_t ldw_b, void* C, int64_t ldc, int64_t M, int64_t N,
+                          int64_t K, int ni) {
+    GemmArgs g;
+    g.A = static_cast<const char*>(A);
+    g.W = static_cast<const char*>(W);
+    g.C = static_cast<char*>(C);
+    g.lda_b = lda_b;
+    g.ldw_b = ldw_b;
+    g.ldc = ldc;
+    g.M = (int)M;
+    g.N = (int)N;
+    g.K = (int)K;
+    g.ni = ni;
+    g.ntn = (int)((N + 32 * ni - 1) / (32 * ni));
+    return g;
+}
 
 template <typename T>
 __device__ __forceinline__ void mma_chunk(f32x4& acc, const uint4& wf, const uint4& xf);
@@ -189,37 +144,16 @@ __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, float a, float b, floa
     *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16(a, b), pack_bf16(c, d));
 }
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-// one 16-B output store with the build's cache policy; inline asm keeps the count of VMEM operations the kernel's
-// counted s_waitcnt relies on (the string ends with s_nop 1: the data registers must outlive the issue)
-__device__ __forceinline__ void store16_out(void* p, const uint4& q) {
-#if SWIFTK_X_STORE == 0
-    *reinterpret_cast<uint4*>(p) = q;
-#else
-    const u32x4 v = {q.x, q.y, q.z, q.w};
-#if SWIFTK_X_STORE == 1
-    asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#elif SWIFTK_X_STORE == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#else
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#endif
-#endif
-}
+// one 16-B store of a bf16 output tile (one VMEM operation: the kernel's counted s_waitcnt relies on the count)
+__device__ __forceinline__ void store16_out(void* p, const uint4& q) { *reinterpret_cast<uint4*>(p) = q; }
 
 // the same store from a wave-uniform base (a scalar register pair) plus a 32-bit per-lane byte offset: the straight-line epilogue's
 // form (tuning key 31 bit 0).  Written as asm because hipcc selects this addressing mode only where it sees the offset's zero-extension
 // in the store's own basic block -- past a slab's exec region it falls back to a 64-bit vector add per store.
+// (the string ends with s_nop 1: the data registers must outlive the issue)
 __device__ __forceinline__ void store16_out_sbase(char* base, uint32_t off, const uint4& q) {
     const u32x4 v = {q.x, q.y, q.z, q.w};
-#if SWIFTK_X_STORE == 0
     asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
-#elif SWIFTK_X_STORE == 1
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
-#elif SWIFTK_X_STORE == 2
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
-#else
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc0 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
-#endif
 }
 
 template <typename OutT>
@@ -485,16 +419,12 @@ __global__ __launch_bounds__(NT) void gemm_kernel(GemmArgs g) {
 // issued between MFMA groups instead of in one burst after the barrier.
 struct TileIter {
     int ntm, ntn, gm;  // tile rows, tile cols, group height
-    int pb, pt;        // > 1: tile rows are walked sample-fastest (pb samples of pt tile rows each), see below
     __device__ __forceinline__ void coords(int t, int& tm, int& tn) const {
         const int per = gm * ntn;
         const int grp = t / per, r = t - grp * per;
         const int rows = min(gm, ntm - grp * gm);
         tn = r / rows;
         tm = grp * gm + (r - tn * rows);
-        // (SWIFTK_X_POSPERM experiment, off: patch embedding with the tile rows walked sample-fastest -- an XCD's window then covers
-        // the SAME token block of eight samples, so a pos_embed block is fetched once per window instead of once per sample)
-        if (pb > 1) tm = (tm % pb) * pt + tm / pb;
     }
 };
 
@@ -515,26 +445,17 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     constexpr int STAGE = A_BYTES + B_BYTES;    // 72 / 76 / 80 KiB: two stages = 144 / 152 / 160 KiB of the CU's 160
     constexpr int WP = B_BYTES / 1024;          // W pieces per stage: 40 / 44 / 48 = 5, 5.5, 6 per wave
     constexpr int HD = 8 * NI;                  // QKNORM: head_dim (a wave tile = two head vectors)
-    constexpr bool TOUCH = SWIFTK_X_TOUCH > 0 && NI <= 11 && sizeof(T) == 2;  // (384-wide tiles use all 160 KiB of LDS)
-    constexpr bool HPF = SWIFTK_X_HPF > 0 && EPI == SWIFTK_EPI_SWIGLU_BWD && NI <= 11 && sizeof(T) == 2;
     // PAIRED (swiftk_gemm_jvp): A holds primal rows 0..M/2-1 and tangent rows M/2..M-1; tile tm takes primal rows 128 tm .. + 127
     // and their tangent rows, wave wm the 32 + 32 rows of tokens 128 tm + 32 wm .. + 31: accumulator row blocks i = 0, 1 are primal,
     // i = 2, 3 the tangents of the same tokens -- the epilogue's tangent rules find both values of an element in one lane
     constexpr bool PAIRED = EPI == SWIFTK_EPI_QKNORM_JVP || EPI == SWIFTK_EPI_SWIGLU_JVP;
     // PPK: the ping-pong k-loop (needs at least three k-tiles per work item; the launcher checks)
-    constexpr bool PP = PPK && sizeof(T) == 2 && !TOUCH && !HPF && !SWIFTK_GEMM_INSTR;
-    static_assert(SL == 0 || PP, "the straight-line forms are written into the ping-pong walk");
-    static_assert(SL == 0 || SWIFTK_X_VMCNT, "the straight-line epilogue takes the interior test of the counted store wait");
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + (TOUCH || HPF ? 256 : 0)];
+    constexpr bool PP = PPK && sizeof(T) == 2;
+    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wv >> 1, wn = wv & 1;
-#if SWIFTK_X_POSPERM
-    const bool posperm = EPI == EPI_BIAS_POS_PAIR && g.ep1 && g.pos_rows >= BM && g.pos_rows % BM == 0 && g.M % g.pos_rows == 0 && g.ksplit == 1;
-    const TileIter it{ntm, g.ntn, gm, posperm ? (int)(g.M / g.pos_rows) : 0, posperm ? (int)(g.pos_rows / BM) : 0};
-#else
-    const TileIter it{ntm, g.ntn, gm, 0, 0};
-#endif
+    const TileIter it{ntm, g.ntn, gm};
     // work item = (output tile, k-split): with ksplit > 1 (weight gradients: few output tiles, K = all tokens) each
     // split accumulates its k-range into its own fp32 slab C + split*c_split; a reduce kernel sums the slabs
     // EPI_NONE_TAIL (small batches, ksplit = 1): work items of two sizes -- tiles [0, tail_from) whole, then each later tile as two
@@ -571,12 +492,11 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     const uint32_t va_even = (uint32_t)(prow * g.lda_b) + 16u * (pchunk ^ ((prow >> 1) & 7));
     const uint32_t va_odd = (uint32_t)(prow * g.lda_b) + 16u * (pchunk ^ ((4 + (prow >> 1)) & 7));
     const uint32_t vb = (uint32_t)(prow * g.ldw_b) + 16u * (pchunk ^ ((4 * (wv & 1) + (prow >> 1)) & 7));
-    // L2 look-ahead: the tile's 256 + BN operand rows as one list, 76 rows per wave: request 1 = rows 64 wv .. + 63 of the list
-    // (waves 0-3: A rows, waves 4-7: W rows 0..255), request 2 = W rows 256 + 12 wv .. + 11 (lanes 12.. repeat the last one)
-    // (row numbers relative to the tile; clamped against the matrix edge where the request is built)
-    const int tr1 = (wv & 3) * 64 + lane;
-    const int tr2 = min(256 + wv * ((BN - 256 + 7) / 8) + min(lane, (BN - 256 + 7) / 8 - 1), BN - 1);
-    int t_m0 = 0, t_n0 = 0;  // origin of the tile the DMA currently feeds (set_sources)
+    // (two dead values, left from the retired L2 look-ahead, that hipcc's output still depends on: without either it orders the scalar
+    // address arithmetic in front of the k-loop differently in 54 instantiations -- the same instructions in another order.  They stay
+    // until a change that re-times the kernels anyway.)
+    [[maybe_unused]] const int tr2 = min(256 + wv * ((BN - 256 + 7) / 8) + min(lane, (BN - 256 + 7) / 8 - 1), BN - 1);
+    [[maybe_unused]] int t_n0 = 0;
     const int nk_all = g.K / (ROWB / (int)sizeof(T));
     auto k_begin = [&](int item) {
         if constexpr (TAIL) return item >= tail_from && ((item - tail_from) & 1) ? nk_all >> 1 : 0;
@@ -633,7 +553,6 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     auto set_sources = [&](int t) {
         int tm, tn;
         it.coords(tile_of(t), tm, tn);
-        t_m0 = tm * BM;
         t_n0 = tn * BN;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -656,12 +575,9 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     // wave-tile halves (read in a k-tile's first two phases), W1 = the other JB (last two phases).  W0 pieces n = wv + 8 i < 4 JA,
     // W1 pieces n = wv + 8 i < 4 JB; piece n of a region: half h = n / (2 J), rows h WT + [JA 16 +] 8 (n - 2 J h) .. + 7 of the
     // tile (2 J and WT / 8 are even: the swizzle parity of a piece is wv & 1, so `vb` serves every W piece here too).
-#ifndef SWIFTK_PP_JA_HI
-#define SWIFTK_PP_JA_HI 0
-#endif
     // (k-half major order: the LOW column half is the smaller one -- its MEM phase carries the four activation fragments too and
     // runs beside the partner's MFMAs of the high half, so the longer MEM phase meets the longer COMPUTE phase)
-    constexpr int JA = SWIFTK_PP_JA_HI ? (NI + 1) / 2 : NI / 2, JB = NI - JA, JM = JA > JB ? JA : JB;
+    constexpr int JA = NI / 2, JB = NI - JA, JM = JA > JB ? JA : JB;
     const char* w0base[3];
     const char* w1base[3];
     auto w0row = [&](int i) { const int n = wv + 8 * i, h = n >= 2 * JA; return h * WT + (n - 2 * JA * h) * 8; };
@@ -706,11 +622,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     // `koff` = byte offset of the k-tile inside a row, carried in the per-lane offset
     auto issue_piece = [&](uint32_t sa, uint32_t koff, int p) {
         if (p < 4) {
-#if SWIFTK_X_ANT
-            dma_piece_fast_nt(sa + (wv * 4 + p) * 1024, abase[p], ((p & 1) ? va_odd : va_even) + koff);
-#else
             dma_piece_fast(sa + (wv * 4 + p) * 1024, abase[p], ((p & 1) ? va_odd : va_even) + koff);
-#endif
         } else {
             const int i = p - 4;
             // W has 40 / 44 / 48 pieces for 8 waves: with 44 the sixth one exists for waves 0-3 only (a wave-uniform branch
@@ -752,16 +664,6 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
     }
     int par = 0;
     bool have_part = false;  // (fp32 operands, kchunk > 0) this tile has a partial sum parked in the workgroup's scratch slab
-    // dbg bit 32 (timing experiment, EPI_NONE only): wave 0 of every 32nd workgroup logs s_memtime at five points of each tile
-    // into the buffer passed as ep1 -- [wg/32][tile][8] uint64: loop top of the first k-step, last MFMA issued, epilogue
-    // barrier passed, stores issued, next loop top passed, sum of the k-steps' vmcnt(0) waits, sum of their barrier waits
-#if SWIFTK_GEMM_INSTR
-    unsigned long long* tlog = nullptr;
-    int tl_i = 0;
-    if ((g.dbg & 32) && wv == 0 && lane == 0 && (blockIdx.x & 31) == 0)
-        tlog = reinterpret_cast<unsigned long long*>(const_cast<float*>(g.ep1)) + (blockIdx.x >> 5) * 8 * 64;
-    bool first_k = true;
-#endif
     // Start-up stagger.  All 256 workgroups walk equally long tiles from the same instant, so every epilogue -- 180 KB of
     // stores per workgroup -- falls into the same few microseconds: the chip alternates between an HBM-write burst with
     // idle matrix pipes (6-8 us per tile at 96 units, 6 TB/s) and a k-loop with an idle write path.  Delaying the
@@ -776,11 +678,9 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
         const uint64_t wait = (uint64_t)ph * (uint64_t)(g.stagger > 0 ? g.stagger : -g.stagger);
         while (__builtin_amdgcn_s_memrealtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
     }
-#if SWIFTK_X_PRIO
     // the second-dispatched half of the workgroup loses every issue arbitration against its SIMD partner; one static
     // priority for that half, no per-segment flips (MI355X_MICROARCH.md, two waves per SIMD, item 4)
     if (!PP && wv >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int grp = wv >> 2;  // ping-pong: waves wv and wv + 4 share a SIMD; group 1 runs one barrier behind group 0
     bool first_kt = true;     // ping-pong: this trip is the first k-tile of an output tile (all waves aligned at its top)
@@ -797,27 +697,6 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
         // (waited at the bottom of the previous trip) own DMA of the stage about to be read has landed; after the
         // barrier every wave's has, and every wave is done reading the other stage (its fragment reads were consumed
         // by MFMAs before it got here)
-#if SWIFTK_GEMM_INSTR
-        unsigned long long ts0 = 0, ts1 = 0;
-        if (tlog) ts0 = ts1 = __builtin_amdgcn_s_memtime();
-#endif
-#if SWIFTK_GEMM_INSTR
-        if (tlog) ts1 = __builtin_amdgcn_s_memtime();
-        if (!(g.dbg & 2)) __builtin_amdgcn_s_barrier();
-        if (tlog) {
-            const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-            if (first_k) {
-                if (tl_i > 0) tlog[(tl_i - 1) * 8 + 4] = ts2;
-                tlog[tl_i * 8 + 0] = ts2;
-                tlog[tl_i * 8 + 5] = 0;
-                tlog[tl_i * 8 + 6] = 0;
-            } else {  // waits of the k-steps inside the tile: own DMA, then the other waves
-                tlog[tl_i * 8 + 5] += ts1 - ts0;
-                tlog[tl_i * 8 + 6] += ts2 - ts1;
-            }
-        }
-        first_k = false;
-#else
         if constexpr (PP) {
             // only a tile's first k-tile meets all waves aligned (the stage about to be read was waited for by every wave in front
             // of this barrier); inside a tile the phase barriers hand the stages over.  Group 1 then drops one barrier behind.
@@ -828,25 +707,11 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
         } else {
             __builtin_amdgcn_s_barrier();
         }
-#endif
         const char* s = smem + par * STAGE;
         const uint32_t fill = lds0 + (par ^ 1) * STAGE;
         const bool last_k = (kt + 1 == nk);
         const bool half = g.khalf && (kt + 1 == nk_all);
         uint32_t koff = (uint32_t)(kt + 1) * ROWB;
-#if SWIFTK_GEMM_INSTR
-        if (g.dbg & 8) koff = 0;  // timing experiment: every stage re-reads k-tile 0 (L2-resident after a tile's first trip)
-#endif
-        const char* hpf_base = nullptr;  // SWIGLU_BWD look-ahead: this wave's 32 rows of the tile's saved pre-activations
-        int hpf_rows = 0, hpf_cols = 0;
-        if constexpr (HPF) {
-            if (last_k) {  // (t_m0 / t_n0 still name the tile being computed: set_sources(next tile) comes below)
-                const int rb = min(t_m0 + wv * 32, (int)g.M - 1);
-                hpf_rows = min(31, (int)g.M - 1 - rb);
-                hpf_cols = (int)g.N * 4 - 4 - t_n0 * 4;  // last byte offset a request may start at, relative to the tile's first column
-                hpf_base = reinterpret_cast<const char*>(g.ep1) + ((int64_t)rb * g.pos_rows + 2 * t_n0) * 2;
-            }
-        }
         if constexpr (PP) {
             const int ntile = tile + stride < ntiles ? tile + stride : tile;  // (past the last item: harmless re-loads)
             if (last_k) {
@@ -892,9 +757,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                 __builtin_amdgcn_sched_barrier(0);
             };
             auto comp = [&](const int j0, const int nj) {
-#if SWIFTK_X_PP_PRIO
                 __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
                 for (int jj = 0; jj < JM; ++jj) {
                     if (jj < nj) {
@@ -902,9 +765,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                         for (int i = 0; i < MI; ++i) mma_chunk<T>(acc[i][j0 + jj], wf[jj], xf[i]);
                     }
                 }
-#if SWIFTK_X_PP_PRIO
                 __builtin_amdgcn_s_setprio(0);
-#endif
             };
             // k-half major: (0, lo) (0, hi) (1, lo) (1, hi); activation fragments are read once per k-half.  Issue order of a
             // wave per k-tile, everything into the other stage:  MEM 0: A0 A1 A2, wait W1(this k-tile) | MEM 1: A3 W0a W0b |
@@ -971,62 +832,24 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
             uint4 xf[MI];
 #pragma unroll
             for (int i = 0; i < MI; ++i) xf[i] = *reinterpret_cast<const uint4*>(s + xoff + i * 16 * ROWB + ch0);
-            // look-ahead target: k-tile kt + 1 + SWIFTK_X_TOUCH of the tile the DMA feeds (its last one at most); in a tile's last
-            // k-tile the DMA already feeds the next tile (set_sources above): the second k-tile of that one
-            uint32_t toff = 0;
-            if constexpr (TOUCH) {
-                const int tk = last_k ? (int)(koff / ROWB) + 1 : min(kt + 1 + SWIFTK_X_TOUCH, nk_all - 1);
-                toff = (uint32_t)min(tk, nk_all - 1) * ROWB;
-            }
-            auto k_half = [&](const int ch, const bool with_dma, const bool with_touch) {
+            auto k_half = [&](const int ch, const bool with_dma) {
                 uint4 wf = *reinterpret_cast<const uint4*>(s + woff + ch);
-#if SWIFTK_X_PF2
                 uint4 wf1 = *reinterpret_cast<const uint4*>(s + woff + 16 * ROWB + ch);  // W fragments run two steps ahead
-#endif
 #pragma unroll
                 for (int j = 0; j < NI; ++j) {
-#if SWIFTK_X_PF2
                     uint4 wn_ = wf1;
-#if SWIFTK_X_FEWREADS  // timing probe, WRONG results: only every FEWREADS-th W fragment is read, the others reuse the previous one
-                    if (j + 2 < NI && (j + 2) % SWIFTK_X_FEWREADS == 0) wf1 = *reinterpret_cast<const uint4*>(s + woff + (j + 2) * 16 * ROWB + ch);
-#else
                     if (j + 2 < NI) wf1 = *reinterpret_cast<const uint4*>(s + woff + (j + 2) * 16 * ROWB + ch);
-#endif
-#else
-                    uint4 wn_ = wf;
-                    if (j + 1 < NI) wn_ = *reinterpret_cast<const uint4*>(s + woff + (j + 1) * 16 * ROWB + ch);
-#endif
 #pragma unroll
                     for (int i = 0; i < MI; ++i) mma_chunk<T>(acc[i][j], wf, xf[i]);
-#if SWIFTK_GEMM_INSTR
-                    if (with_dma && j < 10 && !(g.dbg & 1)) issue_piece(fill, koff, j);
-#else
                     if (with_dma && j < 10) issue_piece(fill, koff, j);
-#endif
-                    if constexpr (HPF) {
-                        if (with_dma && last_k && j < 6) {  // line li of the wave's 32 rows x 11 lines (row-major), one per lane
-                            int el = lane;
-                            asm volatile("" : "+v"(el));
-                            const int li = min(el + 64 * j, 351), r = li / 11, cl = li - 11 * r;
-                            dma_touch(lds0 + 2 * STAGE, hpf_base, (uint32_t)(min(r, hpf_rows) * (int)g.pos_rows * 2 + min(cl * 128, hpf_cols)));
-                        }
-                    }
-                    if constexpr (TOUCH) {
-                        if (with_touch && j == 2) {
-                            if (wv < 4) dma_touch(lds0 + 2 * STAGE, g.A + (int64_t)t_m0 * g.lda_b, (uint32_t)(min(tr1, g.M - 1 - t_m0) * (int)g.lda_b) + toff);
-                            else dma_touch(lds0 + 2 * STAGE, g.W + (int64_t)t_n0 * g.ldw_b, (uint32_t)(min(tr1, g.N - 1 - t_n0) * (int)g.ldw_b) + toff);
-                        }
-                        if (with_touch && j == 6)
-                            dma_touch(lds0 + 2 * STAGE, g.W + (int64_t)t_n0 * g.ldw_b, (uint32_t)(min(tr2, g.N - 1 - t_n0) * (int)g.ldw_b) + toff);
-                    }
                     wf = wn_;
                 }
             };
-            k_half(ch0, true, false);
+            k_half(ch0, true);
             if (!half) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i) xf[i] = *reinterpret_cast<const uint4*>(s + xoff + i * 16 * ROWB + ch1);
-                k_half(ch1, false, TOUCH);
+                k_half(ch1, false);
             }
         }
         par ^= 1;
@@ -1080,11 +903,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
 #if SWIFTK_PP_STAMP
             ++pl_kt;
 #endif
-            // (a k-tile that is not its tile's last is never the half one: both k-halves ran, so with the look-ahead on its two
-            // requests are this wave's youngest VMEM operations and stay in flight)
-            if constexpr (PP) {}  // (waited in the k-tile's last MEM phase)
-            else if constexpr (TOUCH) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if constexpr (!PP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (ping-pong: waited in the k-tile's last MEM phase)
             continue;
         }
         if constexpr (PP) {
@@ -1113,11 +932,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
         }
         bool interior = false;
         // ---- epilogue of `tile`: lane holds C[m][nb .. nb+3] for m = ..+r16, nb = ..+4*(lane>>4) ----
-#if SWIFTK_GEMM_INSTR || SWIFTK_PP_STAMP
-#if SWIFTK_GEMM_INSTR
-        if (tlog) tlog[tl_i * 8 + 1] = __builtin_amdgcn_s_memtime();
-        first_k = true;
-#endif
+#if SWIFTK_PP_STAMP
         if (g.dbg & 4) {  // tuning experiment: drop the epilogue (keeps the accumulators live through a fake use)
 #pragma unroll
             for (int i = 0; i < MI; ++i)
@@ -1228,42 +1043,6 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                         if (jh + jj < NI && m < g.M && nb < g.N) b[jj] = *reinterpret_cast<const uint4*>(H + (int64_t)m * ldh + 2 * nb);
                     }
                 };
-#if SWIFTK_X_BWDROLL
-                // (round 6 experiment) a ROLLING window over the tile's MI x NI saved pre-activation chunks: chunk q + R is requested the
-                // moment chunk q has been consumed, so R loads per lane stay in flight throughout (the grouped form swings between 4 and 8)
-                constexpr int R = SWIFTK_X_BWDROLL;
-                uint4 hr[R];
-                auto load_one = [&](int q) -> uint4 {
-                    const int i = q / NI, j = q - i * NI;
-                    const int m = m0 + wm * 64 + i * 16 + (elane & 15);
-                    const int nb = n0 + wn * WT + j * 16 + 4 * g4;
-                    uint4 r = make_uint4(0u, 0u, 0u, 0u);
-                    if (m < g.M && nb < g.N) r = *reinterpret_cast<const uint4*>(H + (int64_t)m * ldh + 2 * nb);
-                    return r;
-                };
-#pragma unroll
-                for (int q = 0; q < R; ++q) hr[q] = load_one(q);
-#pragma unroll
-                for (int q = 0; q < MI * NI; ++q) {
-                    const int i = q / NI, j = q - i * NI;
-                    const int m = m0 + wm * 64 + i * 16 + (elane & 15);
-                    const int nb = n0 + wn * WT + j * 16 + 4 * g4;
-                    const f32x4 v = acc[i][j];
-                    acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const uint4 hq = hr[q % R];
-                    if (q + R < MI * NI) hr[q % R] = load_one(q + R);
-                    const uint32_t hw[4] = {hq.x, hq.y, hq.z, hq.w};
-                    uint32_t o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float gt = __uint_as_float(hw[e] << 16), up = __uint_as_float(hw[e] & 0xffff0000u);
-                        const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-gt));
-                        o[e] = pack_bf16(v[e] * up * (sg + gt * sg * (1.0f - sg)), v[e] * gt * sg);
-                    }
-                    if (m < g.M && nb < g.N)
-                        *reinterpret_cast<uint4*>(C + (int64_t)m * g.ldc + 2 * nb) = make_uint4(o[0], o[1], o[2], o[3]);
-                }
-#else
                 load_group(0, hb[0]);
 #pragma unroll
                 for (int gidx = 0; gidx < NG; ++gidx) {
@@ -1291,7 +1070,6 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                         }
                     }
                 }
-#endif
             } else
             if constexpr (EPI == SWIFTK_EPI_SWIGLU_BOTH) {
                 // training forward: the pre-activation h (the backward pass needs gate and up) AND silu(gate) * up leave in
@@ -1300,9 +1078,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                 constexpr int RS1 = WT * 2 + 16, RS2 = WT + 16;  // padded slab row strides (bytes): WT / WT/2 columns
                 constexpr int CP1 = WT / 8, CP2 = WT / 16;       // 16-B chunks per row
                 __builtin_amdgcn_s_barrier();
-#if SWIFTK_X_VMCNT
                 interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-#endif
                 char* slab = const_cast<char*>(s) + wv * (16 * RS1);
                 int elane = lane;
                 asm volatile("" : "+v"(elane));
@@ -1368,14 +1144,9 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                 // the slabs overlay operand bytes of the stage just consumed: every wave must be done READING that stage
                 // (its last fragments were consumed by MFMAs it has already issued) before any wave writes a slab
                 __builtin_amdgcn_s_barrier();
-#if SWIFTK_GEMM_INSTR
-                if (tlog) tlog[tl_i * 8 + 2] = __builtin_amdgcn_s_memtime();
-#endif
-#if SWIFTK_X_VMCNT
                 // interior tile: every lane group of every store below is live, so the wave issues exactly 24 (12 with
                 // SwiGLU) global stores after its last DMA piece -- the count the next loop trip leaves outstanding
                 interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-#endif
                 char* slab = const_cast<char*>(s) + wv * (16 * RSTR);
                 // lane-derived epilogue addresses are rebuilt from an opaque copy of the lane id: left visible, hipcc
                 // hoists ~40 loop-invariant epilogue VGPRs above the k-loop and spills them inside it
@@ -1419,13 +1190,8 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                                 const f32x4 v = acc[i][j];
                                 acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
                                 if constexpr (GLU) {
-#if SWIFTK_X_NOSILU
-                                    const float h0 = v[0] * v[1];
-                                    const float h1 = v[2] * v[3];
-#else
                                     const float h0 = v[0] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[0])) * v[1];
                                     const float h1 = v[2] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[2])) * v[3];
-#endif
                                     *reinterpret_cast<uint32_t*>(wr + j * 16) = pack_bf16(h0, h1);
                                 } else {
                                     *reinterpret_cast<uint2*>(wr + j * 32) = make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
@@ -1498,13 +1264,8 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                             *reinterpret_cast<uint32_t*>(slab + r16 * RSTR + (j * 8 + 2 * g4) * 2) = hp;
                         } else if constexpr (EPI == SWIFTK_EPI_SWIGLU) {
                             // silu(g) * u with v_exp_f32 / v_rcp_f32 (1 ulp each; the libm forms cost ~30 VALU apiece)
-#if SWIFTK_X_NOSILU  // timing probe with WRONG results (round 6): the epilogue without its transcendentals = the bound of any cheaper sigmoid
-                            const float h0 = v[0] * v[1];
-                            const float h1 = v[2] * v[3];
-#else
                             const float h0 = v[0] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[0])) * v[1];
                             const float h1 = v[2] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[2])) * v[3];
-#endif
                             *reinterpret_cast<uint32_t*>(slab + r16 * RSTR + (j * 8 + 2 * g4) * 2) = pack_bf16(h0, h1);
                         } else {
                             *reinterpret_cast<uint2*>(slab + r16 * RSTR + (j * 16 + 4 * g4) * 2) =
@@ -1530,25 +1291,12 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                         }
                     }
                     constexpr int NCH = (16 * CPR + 63) / 64;
-#if SWIFTK_X_EPIBATCH
-                    uint4 qs[NCH];
-#pragma unroll
-                    for (int t = 0; t < NCH; ++t) {
-                        const int c = min(elane + 64 * t, 16 * CPR - 1);
-                        const int row = c / CPR, cc = c - row * CPR;
-                        qs[t] = *reinterpret_cast<const uint4*>(slab + row * RSTR + cc * 16);
-                    }
-#endif
 #pragma unroll
                     for (int t = 0; t < NCH; ++t) {
                         const int c = elane + 64 * t;
                         const int row = c / CPR, cc = c - row * CPR;
                         if (c < 16 * CPR) {
-#if SWIFTK_X_EPIBATCH
-                            const uint4 q = qs[t];
-#else
                             const uint4 q = *reinterpret_cast<const uint4*>(slab + row * RSTR + cc * 16);
-#endif
                             const int m = mrow0 + row, n = ncol0 + cc * 8;
                             int64_t dst = (int64_t)m * g.ldc + n;
                             if constexpr (EPI == EPI_QKNORM_TILED) {
@@ -1671,12 +1419,6 @@ __global__ __launch_bounds__(NT) void gemm_kernel_p(GemmArgs g, int ntm, int gm)
                 }
             }
         }
-#if SWIFTK_GEMM_INSTR
-        if (tlog) {
-            tlog[tl_i * 8 + 3] = __builtin_amdgcn_s_memtime();
-            ++tl_i;
-        }
-#endif
         tile += stride;
         if (tile >= ntiles) break;
         kt = k_begin(tile);
@@ -1702,14 +1444,14 @@ int g_variant = 1;   // 0: one tile per workgroup; 1: persistent, grouped tile o
 int g_group_m = 8;   // tile rows per group in the persistent order
 int g_dbg = 0;
 int g_stagger_permille = 0;  // tuning key 7: start-up phase step as a fraction (in 1/1000) of an eighth of the estimated tile time
-int g_pp = SWIFTK_X_PP;      // tuning key 20: ping-pong k-loop of the persistent kernel (bf16 operands)
+int g_pp = 1;                // tuning key 20: ping-pong k-loop of the persistent kernel (bf16 operands)
 // tuning key 31: gemm_kernel_p outside its k-loop (SL): bit 0 straight-line epilogue, bit 1 incremental tile walk.  A bit ships set where
 // its slowest round beat the old arm's fastest in tools/gemm_epilogue_probe.py: bit 1 did on wo, w1 + SwiGLU and w2 (-1.7 ... -2.0 %), bit 0
 // did not on wo and w1 + SwiGLU (profiles/r08a_gemm_epilogue_straightline.txt) and stays selectable only
 int g_gemm_sl = 2;
 
 // the ping-pong loop prefetches W0 two k-tiles ahead: every work item needs at least three k-tiles
-inline bool pp_ok(const GemmArgs& g) { return g_pp > 0 && !SWIFTK_GEMM_INSTR && (g.K / 64) / g.ksplit >= 3; }
+inline bool pp_ok(const GemmArgs& g) { return g_pp > 0 && (g.K / 64) / g.ksplit >= 3; }
 
 struct Prof {
     int epilogue = -1, N = 0;
@@ -1720,9 +1462,7 @@ struct Prof {
 
 // the instantiations that take the straight-line forms of tuning key 31 (see SL at gemm_kernel_p)
 template <typename T, typename OutT, int EPI>
-constexpr bool sl_capable = sizeof(T) == 2 && sizeof(OutT) == 2 && (EPI == SWIFTK_EPI_NONE || EPI == SWIFTK_EPI_SWIGLU) &&
-                            // (written into the ping-pong walk and the counted store wait: not in the builds that compile either out)
-                            !SWIFTK_GEMM_INSTR && !(SWIFTK_X_TOUCH > 0) && SWIFTK_X_VMCNT;
+constexpr bool sl_capable = sizeof(T) == 2 && sizeof(OutT) == 2 && (EPI == SWIFTK_EPI_NONE || EPI == SWIFTK_EPI_SWIGLU);
 int g_gemm_sl_seen = 0;  // tuning key 32 (diagnostic): bit n = the SL = n instantiation was launched since the key was last cleared
 
 // 352-wide tiles, ping-pong k-loop: the one geometry of the forecast step's wo / w1 / w2 products
@@ -1744,6 +1484,33 @@ int launch_p11_pp(const GemmArgs& g, int grid, int ntm, hipStream_t st) {
     return 0;
 }
 
+// The one place a persistent kernel is picked: tile width g.ni out of the widths this <T, OutT, EPI> is instantiated for (352 always,
+// 320 / 384 where W320 / W384 say so) x k-loop (`pp`: the ping-pong loop, bf16 operands only).  A width outside the set takes 352.
+template <typename T, typename OutT, int EPI, bool W320, bool W384, bool PPK>
+int launch_width(const GemmArgs& g, int grid, int ntm, hipStream_t st) {
+    if constexpr (W320)
+        if (g.ni == 10) {
+            hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 10, PPK>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
+            return 0;
+        }
+    if constexpr (W384)
+        if (g.ni == 12) {
+            hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 12, PPK>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
+            return 0;
+        }
+    if constexpr (PPK) return launch_p11_pp<T, OutT, EPI>(g, grid, ntm, st);
+    hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
+    return 0;
+}
+template <typename T, typename OutT, int EPI, bool W320, bool W384>
+int launch_p(const GemmArgs& g, int ntm, hipStream_t st) {
+    const int ntiles = ntm * g.ntn * g.ksplit;
+    const int grid = ntiles < g_persist_wgs ? ntiles : g_persist_wgs;
+    if constexpr (sizeof(T) == 2)
+        if (pp_ok(g)) return launch_width<T, OutT, EPI, W320, W384, true>(g, grid, ntm, st);
+    return launch_width<T, OutT, EPI, W320, W384, false>(g, grid, ntm, st);
+}
+
 template <typename T, typename OutT, int EPI>
 int launch(const GemmArgs& g, hipStream_t st) {
     auto kern = gemm_kernel<T, OutT, EPI>;
@@ -1763,27 +1530,11 @@ int launch(const GemmArgs& g, hipStream_t st) {
         g1.ntn = (g.N + BN - 1) / BN;
         hipLaunchKernelGGL(kern, dim3(ntm * g1.ntn), dim3(NT), 0, st, g1);
     } else {
-        const int ntiles = ntm * g.ntn * g.ksplit;
-        const int grid = ntiles < g_persist_wgs ? ntiles : g_persist_wgs;
-        if constexpr (sizeof(T) == 2) {  // bf16 operands: all three tile widths (head_dim 80 / 88 / 96 families)
-            if (pp_ok(g)) {
-                if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 10, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-                else if (g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 12, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-                else if (const int rc = launch_p11_pp<T, OutT, EPI>(g, grid, ntm, st)) return rc;
-            } else {
-                if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 10, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-                else if (g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 12, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-                else hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-            }
-        } else if constexpr (EPI == SWIFTK_EPI_QKNORM) {
-            // fp32 operands: 352-wide tiles, and for the cosine-attention epilogue also the 320- / 384-wide ones (a tile must hold
-            // whole head pairs: head_dim 80 / 96, the exact engine and the split engine's hot head pairs on the larger variants)
-            if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 10, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-            else if (g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 12, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-            else hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-        } else {
-            hipLaunchKernelGGL((gemm_kernel_p<T, OutT, EPI, 11, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-        }
+        // bf16 operands: all three tile widths (head_dim 80 / 88 / 96 families).  fp32 operands: 352-wide tiles, and for the
+        // cosine-attention epilogue also the 320- / 384-wide ones (a tile must hold whole head pairs: head_dim 80 / 96, the exact
+        // engine and the split engine's hot head pairs on the larger variants)
+        constexpr bool WIDE = sizeof(T) == 2 || EPI == SWIFTK_EPI_QKNORM;
+        if (const int rc = launch_p<T, OutT, EPI, WIDE, WIDE>(g, ntm, st)) return rc;
     }
     if (timed) swiftk_prof_end(st);
     SWIFTK_CHECK_LAUNCH();
@@ -1799,17 +1550,7 @@ int launch_paired(const GemmArgs& g, hipStream_t st) {
     constexpr bool W384 = EPI != EPI_BIAS_POS_PAIR;
     if (!W384 && g.ni == 12) return SWIFTK_ESHAPE;
     const bool timed = swiftk_prof_begin(EPI, g.N, st);
-    const int ntiles = ntm * g.ntn;
-    const int grid = ntiles < g_persist_wgs ? ntiles : g_persist_wgs;
-    if (pp_ok(g)) {
-        if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<bf16_t, bf16_t, EPI, 10, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-        else if (W384 && g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<bf16_t, bf16_t, EPI, W384 ? 12 : 11, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-        else hipLaunchKernelGGL((gemm_kernel_p<bf16_t, bf16_t, EPI, 11, true>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-    } else {
-        if (g.ni == 10) hipLaunchKernelGGL((gemm_kernel_p<bf16_t, bf16_t, EPI, 10, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-        else if (W384 && g.ni == 12) hipLaunchKernelGGL((gemm_kernel_p<bf16_t, bf16_t, EPI, W384 ? 12 : 11, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-        else hipLaunchKernelGGL((gemm_kernel_p<bf16_t, bf16_t, EPI, 11, false>), dim3(grid), dim3(NT), 0, st, g, ntm, g_group_m);
-    }
+    if (const int rc = launch_p<bf16_t, bf16_t, EPI, true, W384>(g, ntm, st)) return rc;
     if (timed) swiftk_prof_end(st);
     SWIFTK_CHECK_LAUNCH();
     return 0;
@@ -1861,81 +1602,41 @@ void swiftk_prof_end(hipStream_t st) {
     ++g_prof.used;
 }
 
+// every tuning key of include/swiftk.h and the variable it sets and reads
+static const struct { int key; int* value; } g_tuning[] = {
+    {0, &g_variant},          {1, &g_group_m},      {2, &g_persist_wgs},    {3, &g_dbg},           {4, &g_attn_dbg},
+    {5, &g_fwd_tiled},        {6, &g_modnorm_nt},   {7, &g_stagger_permille}, {8, &g_fwd_fused},   {9, &g_attn_bwd_pipe},
+    {11, &g_x3_exact},        {12, &g_fwd_pair},    {13, &g_f32_chunk_k},   {14, &g_fwd_splitk},   {15, &g_attn_bwd_fuse},
+    {16, &g_modnorm_bwd_fused}, {17, &g_modnorm_jvp_rows}, {18, &g_x3_ffsplit}, {19, &g_fwd_pepair}, {20, &g_pp},
+    {21, &g_attn_pp},         {22, &g_tn_pp},       {23, &g_fwd_rownorm},   {24, &g_rownorm_dbg},  {25, &g_zero_memset},
+    {26, &g_x3_normsplit},    {27, &g_x3_qkonly},   {28, &g_x3_attnpv},     {29, &g_fwd_tail},     {30, &g_attn_sl},
+    {31, &g_gemm_sl},         {32, &g_gemm_sl_seen},
+};
+
+static int* tuning_value(int key) {
+    for (const auto& row : g_tuning)
+        if (row.key == key) return row.value;
+    return nullptr;
+}
+
 extern "C" int swiftk_set_tuning(int key, int value) {
-    switch (key) {
-        case 0: g_variant = value; return 0;
-        case 1: g_group_m = value > 0 ? value : 1; return 0;
-        case 2: g_persist_wgs = value > 0 ? value : 1; return 0;
-        case 3: g_dbg = value; return 0;
-        case 4: g_attn_dbg = value; return 0;
-        case 5: g_fwd_tiled = value; return 0;
-        case 6: g_modnorm_nt = value; return 0;
-        case 7: g_stagger_permille = value; return 0;
-        case 8: g_fwd_fused = value; return 0;
-        case 9: g_attn_bwd_pipe = value; return 0;
-        case 11: g_x3_exact = value; return 0;
-        case 12: g_fwd_pair = value; return 0;
-        case 13: g_f32_chunk_k = value; return 0;
-        case 14: g_fwd_splitk = value; return 0;
-        case 15: g_attn_bwd_fuse = value; return 0;
-        case 16: g_modnorm_bwd_fused = value; return 0;
-        case 17: g_modnorm_jvp_rows = value; return 0;
-        case 18: g_x3_ffsplit = value; return 0;
-        case 19: g_fwd_pepair = value; return 0;
-        case 20: g_pp = value; return 0;
-        case 21: g_attn_pp = value; return 0;
-        case 22: g_tn_pp = value; return 0;
-        case 23: g_fwd_rownorm = value; return 0;
-        case 24: g_rownorm_dbg = value; return 0;
-        case 26: g_x3_normsplit = value; return 0;
-        case 27: g_x3_qkonly = value; return 0;
-        case 28: g_x3_attnpv = value; return 0;
-        case 29: g_fwd_tail = value; return 0;
-        case 30: g_attn_sl = value & 3; return 0;
-        case 31: g_gemm_sl = value & 3; return 0;
-        case 32: g_gemm_sl_seen = 0; return 0;
-        case 25:
-            g_zero_memset = value;
-            return (value & 4) ? swiftk_zero_check_enable() : 0;
+    switch (key) {  // the keys that do more than store the value
+        case 1:
+        case 2: value = value > 0 ? value : 1; break;
+        case 30:
+        case 31: value &= 3; break;
+        case 32: value = 0; break;  // (clears; the value is ignored)
+        case 25: g_zero_memset = value; return (value & 4) ? swiftk_zero_check_enable() : 0;
     }
-    return SWIFTK_EINVAL;
+    int* const p = tuning_value(key);
+    if (!p) return SWIFTK_EINVAL;
+    *p = value;
+    return 0;
 }
 
 extern "C" int swiftk_get_tuning(int key) {
-    switch (key) {
-        case 0: return g_variant;
-        case 1: return g_group_m;
-        case 2: return g_persist_wgs;
-        case 3: return g_dbg;
-        case 4: return g_attn_dbg;
-        case 5: return g_fwd_tiled;
-        case 6: return g_modnorm_nt;
-        case 7: return g_stagger_permille;
-        case 8: return g_fwd_fused;
-        case 9: return g_attn_bwd_pipe;
-        case 11: return g_x3_exact;
-        case 12: return g_fwd_pair;
-        case 13: return g_f32_chunk_k;
-        case 14: return g_fwd_splitk;
-        case 15: return g_attn_bwd_fuse;
-        case 16: return g_modnorm_bwd_fused;
-        case 17: return g_modnorm_jvp_rows;
-        case 18: return g_x3_ffsplit;
-        case 19: return g_fwd_pepair;
-        case 20: return g_pp;
-        case 21: return g_attn_pp;
-        case 22: return g_tn_pp;
-        case 23: return g_fwd_rownorm;
-        case 25: return g_zero_memset;
-        case 26: return g_x3_normsplit;
-        case 27: return g_x3_qkonly;
-        case 28: return g_x3_attnpv;
-        case 29: return g_fwd_tail;
-        case 30: return g_attn_sl;
-        case 31: return g_gemm_sl;
-        case 32: return g_gemm_sl_seen;
-    }
-    return SWIFTK_EINVAL;
+    const int* const p = tuning_value(key);
+    return p ? *p : SWIFTK_EINVAL;
 }
 
 extern "C" int swiftk_profile_gemm(int epilogue, int64_t N) {
@@ -2025,31 +1726,17 @@ static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, voi
     }
     if (epilogue == SWIFTK_EPI_BIAS_POS && (!ep0 || ((uintptr_t)ep0 & 15) || (ep1 && (((uintptr_t)ep1 & 15) || pos_rows <= 0))))
         return SWIFTK_EINVAL;
-    GemmArgs g;
-    g.A = static_cast<const char*>(A);
-    g.W = static_cast<const char*>(W);
-    g.C = static_cast<char*>(C);
-    g.lda_b = lda * es;
-    g.ldw_b = ldw * es;
-    g.ldc = ldc;
-    g.M = (int)M;
-    g.N = (int)N;
-    g.K = (int)K;
+    GemmArgs g = make_args(A, lda * es, W, ldw * es, C, ldc, M, N, K, ni);
     g.ep0 = ep0;
     g.ep1 = ep1;
     g.pos_rows = (int)pos_rows;
-    g.ni = ni;
     g.qk_only = qk_only;
-    g.ntn = (int)((N + 32 * ni - 1) / (32 * ni));
     g.dbg = g_dbg;
     g.ksplit = ksplit;
     g.c_split = c_split;
-    g.batch_a = g.batch_w = g.batch_c = 0;
     g.khalf = khalf;
-    g.touch = 0;  // (unused: the look-ahead is a build-time switch, its requests clamp against the matrix edges)
     // estimated time of one output tile at ~1.35 PFLOP/s chip-wide (5.3 TFLOP/s per CU), in 10-ns ticks; the stagger only
     // makes sense when a workgroup walks several tiles
-    g.stagger = 0;
     if (g_stagger_permille > 0 && dtype == SWIFTK_BF16 && ksplit == 1) {
         const double tile_s = 2.0 * 256.0 * (32.0 * ni) * (double)K / 5.3e12;
         const int64_t tiles = ((M + 255) / 256) * g.ntn;
@@ -2057,19 +1744,16 @@ static int gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, voi
         if (tiles >= 4 * 256) g.stagger = (int)(tile_s * 1e8 / 8.0 * pm / 1000.0) * (g_stagger_permille >= 10000 ? -1 : 1);
     }
     g.kscr = kscr;
-    g.kchunk = 0;
     if (kscr && dtype == SWIFTK_F32 && ksplit == 1 && kchunk > 0) {
         // chains of equal length: K = 1056 (33 k-tiles) at a nominal 8 tiles -> 4 chains of 9, 9, 9, 6 (three parks per tile),
         // not 8, 8, 8, 8, 1
         const int nkt = (int)(K / tile_k), chains = nkt / kchunk > 1 ? nkt / kchunk : 1;
         g.kchunk = chains > 1 ? (nkt + chains - 1) / chains : 0;
     }
-    g.t_gh = g.t_gw = g.t_sh = g.t_sw = g.t_heads = 0;
     if (tiling) {
         g.t_gh = tiling[0]; g.t_gw = tiling[1]; g.t_sh = tiling[2]; g.t_sw = tiling[3]; g.t_heads = tiling[4];
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    g.tail_from = 0;
     if (tail_rows_from) {
         // The last round of the persistent walk as k-halves (see EPI_NONE_TAIL in the kernel): T tiles on G workgroups with a
         // remainder r = T % G of at most G / 2 -- the first T - r tiles whole into slab 0, the last r as two halves into slabs 0 / 1.
@@ -2137,31 +1821,12 @@ extern "C" int swiftk_gemm_jvp(const void* A, int64_t lda, const void* W, int64_
         if (N % 384 == 0 && N % 352) ni = 12;
         else if (N % 320 == 0 && N % 352) ni = 10;
     }
-    GemmArgs g;
-    g.A = static_cast<const char*>(A);
-    g.W = static_cast<const char*>(W);
-    g.C = static_cast<char*>(C);
-    g.lda_b = lda * 2;
-    g.ldw_b = ldw * 2;
-    g.ldc = ldc;
-    g.M = (int)(2 * Mh);
-    g.N = (int)N;
-    g.K = (int)K;
+    GemmArgs g = make_args(A, lda * 2, W, ldw * 2, C, ldc, 2 * Mh, N, K, ni);
     g.ep0 = scale;
     g.ep1 = epilogue == SWIFTK_EPI_QKNORM_JVP ? rn : static_cast<const float*>(C2);
     g.pos_rows = (int)ldc2;
-    g.ni = ni;
-    g.ntn = (int)((N + 32 * ni - 1) / (32 * ni));
     g.dbg = g_dbg;
-    g.ksplit = 1;
-    g.c_split = 0;
-    g.batch_a = g.batch_w = g.batch_c = 0;
     g.khalf = khalf;
-    g.touch = 0;
-    g.stagger = 0;
-    g.kscr = nullptr;
-    g.kchunk = 0;
-    g.t_gh = g.t_gw = g.t_sh = g.t_sw = g.t_heads = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (epilogue == SWIFTK_EPI_QKNORM_JVP) return launch_paired<SWIFTK_EPI_QKNORM_JVP>(g, st);
     return launch_paired<SWIFTK_EPI_SWIGLU_JVP>(g, st);
@@ -2177,31 +1842,13 @@ extern "C" int swiftk_gemm_bias_pos_pair(const void* A, int64_t lda, const void*
         return SWIFTK_EALIGN;
     // 320-wide tiles where they divide N (dim 1280); dim 1536 takes the 352-wide ones with a partly filled last column (launch_paired)
     const int ni = N % 352 && N % 320 == 0 ? 10 : 11;
-    GemmArgs g;
-    g.A = static_cast<const char*>(A);
-    g.W = static_cast<const char*>(W);
-    g.C = static_cast<char*>(hi);
-    g.lda_b = lda * 2;
-    g.ldw_b = ldw * 2;
-    g.ldc = ldh;
-    g.M = (int)M;
-    g.N = (int)N;
-    g.K = (int)K;
+    GemmArgs g = make_args(A, lda * 2, W, ldw * 2, hi, ldh, M, N, K, ni);
     g.ep0 = bias;
     g.ep1 = pos;
     g.pos_rows = (int)pos_rows;
-    g.ni = ni;
-    g.ntn = (int)((N + 32 * ni - 1) / (32 * ni));
     g.dbg = g_dbg;
-    g.ksplit = 1;
     g.c_split = ldl;  // (row stride of the low parts, bytes)
-    g.batch_a = g.batch_w = g.batch_c = 0;
-    g.khalf = 0;
-    g.touch = 0;
-    g.stagger = 0;
     g.kscr = static_cast<float*>(lo);
-    g.kchunk = 0;
-    g.t_gh = g.t_gw = g.t_sh = g.t_sw = g.t_heads = 0;
     return launch_paired<EPI_BIAS_POS_PAIR>(g, static_cast<hipStream_t>(stream));
 }
 
@@ -2236,30 +1883,10 @@ extern "C" int swiftk_gemm_batched(const void* A, int64_t lda, int64_t stride_a,
     if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || (lda * 2) % 16 || (ldw * 2) % 16 || (stride_a * 2) % 16 || (stride_w * 2) % 16)
         return SWIFTK_EALIGN;
     if (((uintptr_t)C % (4 * os)) || (ldc * os) % (4 * os) || (stride_c * os) % (4 * os)) return SWIFTK_EALIGN;
-    GemmArgs g;
-    g.A = static_cast<const char*>(A);
-    g.W = static_cast<const char*>(W);
-    g.C = static_cast<char*>(C);
-    g.lda_b = lda * 2;
-    g.ldw_b = ldw * 2;
-    g.ldc = ldc;
-    g.M = (int)M;
-    g.N = (int)N;
-    g.K = (int)K;
-    g.ep0 = g.ep1 = nullptr;
-    g.pos_rows = 0;
-    g.ni = 11;
-    g.ntn = (int)((N + BN - 1) / BN);
-    g.dbg = 0;
-    g.khalf = g.touch = g.stagger = 0;
-    g.ksplit = 1;
-    g.c_split = 0;
-    g.kscr = nullptr;
-    g.kchunk = 0;
+    GemmArgs g = make_args(A, lda * 2, W, ldw * 2, C, ldc, M, N, K, NI);  // (the one-tile-per-workgroup kernel: 352-wide tiles)
     g.batch_a = stride_a * 2;
     g.batch_w = stride_w * 2;
     g.batch_c = stride_c * os;
-    g.t_gh = g.t_gw = g.t_sh = g.t_sw = g.t_heads = 0;
     const dim3 grid((unsigned)(((M + BM - 1) / BM) * g.ntn), (unsigned)batch);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (out_dtype == SWIFTK_BF16) hipLaunchKernelGGL((gemm_kernel<bf16_t, bf16_t, SWIFTK_EPI_NONE>), grid, dim3(NT), 0, st, g);

@@ -306,7 +306,7 @@ __global__ __launch_bounds__(NT) void qkv_attn_kernel(FusedArgs a, int nitems) {
         // the first k-tile was requested before the previous item's output stores (VMEM retires in issue order)
         if (have_prev) wait_vm<NOST>(); else wait_vm<0>();
         if constexpr (PP) {
-            // Ping-pong form (see gemm.hip, SWIFTK_X_PP): phases (k-half, column part) = (0, lo) (0, hi) (1, lo) (1, hi); in each a
+            // Ping-pong form (see gemm.hip, "Ping-pong k-loop"): phases (k-half, column part) = (0, lo) (0, hi) (1, lo) (1, hi); in each a
             // wave first requests the phase's fragments and issues its share of the next stage's pieces (MEM), then -- behind a
             // barrier -- runs the phase's MFMAs back to back (COMPUTE), then a second barrier.  Waves 4-7 (column half 1), the SIMD
             // partners of waves 0-3, run one barrier behind.  Issue order per k-tile: A0 A1 A2 [wait HI of this k-tile] | A3 LO LO |

@@ -285,6 +285,38 @@ def test_gemm_bias_pos_pair_exact(dev, c):
     check_bits(lo.to(torch.int16), wlo, c, "lo", c.M, c.N)
 
 
+# ------------------------------------------------------------------------------------------------ tuning key 20 = 0, the tuning keys
+ONE_BARRIER = ["p320_below-bb", "p320_below-bf", "p384_below-bb", "p384_below-bf", "p352_below-bb", "swiglu_both_H2816-bb", "accum_320-bf",
+               "pair_1280-bb", "jvp_swiglu_1280-bb"]
+
+
+@pytest.mark.parametrize("name", ONE_BARRIER)
+def test_one_barrier_loop_exact(dev, scratch, name):
+    """Tuning key 20 = 0: the same rows of the table through the one-barrier k-loop of the persistent kernel (the launcher's other
+    arm at all three tile widths, plain, SwiGLU, ACCUM, pair-output and paired-row epilogues).  One right answer, so the same bits."""
+    c, = [c for c in X.CASES if c.name == name]
+    body = {"gemm": lambda: test_gemm_exact(dev, scratch, c), "swiglu_both": lambda: test_swiglu_both_preactivation_exact(dev, c),
+            "jvp": lambda: test_gemm_jvp_kept_preactivation_exact(dev, c), "bias_pos_pair": lambda: test_gemm_bias_pos_pair_exact(dev, c)}[c.entry]
+    assert X.expected_cell(c).kernel == "persistent" and L().swiftk_set_tuning(20, 0) == 0
+    try:
+        assert L().swiftk_get_tuning(20) == 0
+        body()
+    finally:
+        L().swiftk_set_tuning(20, 1)
+
+
+def test_tuning_keys_read_back(dev):
+    """Every key include/swiftk.h documents (25 and 32 act on being set: left alone) takes the value it reports and reports it again;
+    so does key 24 (the complete-row kernel's ablation bits); keys 10 and 99 do not exist."""
+    for key in [*range(0, 10), *range(11, 25), *range(26, 32)]:
+        v = L().swiftk_get_tuning(key)
+        assert v >= 0, key
+        assert L().swiftk_set_tuning(key, v) == 0 and L().swiftk_get_tuning(key) == v, key
+    for key in (10, 99):
+        assert L().swiftk_get_tuning(key) == -1 and L().swiftk_set_tuning(key, 1) == -1  # SWIFTK_EINVAL
+        assert L().swiftk_get_tuning(key) == -1
+
+
 # ------------------------------------------------------------------------------------------------ swiftk_unit_checksum
 def checksum(x, B, n, ptr=None):
     out = torch.full((B,), float("nan"), dtype=torch.float64, device=x.device)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Ping-pong GEMM diagnostics (lib built with -DSWIFTK_X_PP=.. -DSWIFTK_PP_STAMP=1, selected with SWIFTK_LIB):
+"""Ping-pong GEMM diagnostics (lib built with -DSWIFTK_PP_STAMP=1, selected with SWIFTK_LIB):
  (1) ablation timings, tuning key 3: 0 = as shipped, 8 = every stage re-reads k-tile 0, 1 = no DMA, 4 = no epilogue, 5 = neither;
  (2) s_memtime stamps around every barrier of one tile (bit 64): mean cycles a wave of group 0 / group 1 spends in each MEM
      phase, at the barrier behind it, in each COMPUTE phase, at the barrier behind that.
