@@ -577,6 +577,26 @@ int swiftk_rmse_sums(const float* y, const float* t, int64_t t_batch_stride, con
 #define SWIFTK_SWEEP_SLICES 8
 int swiftk_sweep_sse(const float* xstd, int64_t x_batch_stride, const float* y, const float* t, const float* mx, const float* sx,
                      const float* st, const double* w_lat, double* out, double* scratch, int B, int C, int H, int W, void* stream);
+/* Zonal power spectra of field planes (the sharpness evidence of `generate --spectra`).  A plane is x[h, w], H latitudes and W
+ * longitudes, W even; wavenumbers k = 0 .. W/2, K = W/2 + 1:
+ *   X_h(k) = sum_w x[h,w] exp(-2 pi i k w / W)
+ *   P_h(k) = c_k |X_h(k)|^2 / W^2,  c_0 = c_{W/2} = 1, otherwise 2      (one-sided: sum_k P_h(k) = mean_w x[h,w]^2)
+ *   P(k)   = (1/H) sum_h w_lat[h] P_h(k),  w_lat = cos(lat) / mean(cos(lat))
+ * so that sum_k P(k) is the latitude-weighted mean square of the plane (Parseval).  x [n, G, V, H, W] fp32 contiguous; with G > 1
+ * the transform is taken of the mean over the G consecutive planes (the members: the ensemble mean's spectrum), the members added
+ * in member order in fp64 and multiplied by 1/G.  w_lat [H] and twiddle [W][2] = (cos, sin)(2 pi j / W) are fp64, computed by the
+ * caller; out [n, V, K] fp64.  Everything after the load is fp64 -- the row values, the products with the table entry
+ * (k w) mod W (the index advances by add and conditional subtract: W need not be a power of two), the sums over w, the squares and
+ * the sum over rows: an atmospheric spectrum's interesting bins lie six and more orders of magnitude below its total, and a field
+ * like temperature carries a mean of 280 under waves of 1e-2, which an fp32 transform loses.
+ * One workgroup per (n, v) plane walks its rows in order; no atomics, no scratch buffer, and out is written completely by every
+ * call (no clearing).  The bits of a plane's row of out depend on (G, H, W) and the plane's values only -- not on n, V, the
+ * plane's position in the batch or the rank.
+ * Refused before any launch: a null pointer or a non-positive size (SWIFTK_EINVAL); W odd, W < 4, W > 2048 (the LDS staging of
+ * row group and table) or n V above 2^31 - 1 (SWIFTK_ESHAPE); x off a 4-byte boundary or a double pointer off an 8-byte one
+ * (SWIFTK_EALIGN). */
+int swiftk_zonal_power(const float* x, const double* w_lat, const double* twiddle, double* out, int n, int G, int V, int H, int W,
+                       void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
  * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host. */

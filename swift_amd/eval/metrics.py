@@ -34,6 +34,41 @@ def ensemble_sums(pred: torch.Tensor, y: torch.Tensor, lat) -> torch.Tensor:
     return out
 
 
+_SPECTRUM_TABLES: dict = {}  # (W, latitudes, device) -> (w_lat [H], twiddle [W, 2]) fp64 on the device
+
+
+def _spectrum_tables(W: int, lat, device):
+    lat = np.ascontiguousarray(lat, dtype=np.float64)
+    key = (W, lat.tobytes(), str(device))
+    if key not in _SPECTRUM_TABLES:
+        w = np.cos(np.deg2rad(lat))
+        a = 2.0 * np.pi * np.arange(W, dtype=np.float64) / W
+        _SPECTRUM_TABLES[key] = (torch.from_numpy(w / w.mean()).to(device),
+                                 torch.from_numpy(np.stack([np.cos(a), np.sin(a)], 1)).to(device).contiguous())
+    return _SPECTRUM_TABLES[key]
+
+
+def zonal_power(fields: torch.Tensor, lat, group: int = 1) -> torch.Tensor:
+    """Latitude-weighted one-sided zonal power spectra, wavenumbers 0 .. W/2 (definition: include/swiftk.h,
+    ``swiftk_zonal_power``; summed over k a spectrum is the plane's latitude-weighted mean square).  fields [n, group, V, H, W]
+    (or [n, V, H, W] when ``group == 1``), fp32 on the device -> [n, V, W/2 + 1] fp64 on the device; with ``group > 1`` the
+    spectrum is that of the mean over the ``group`` consecutive planes (the members of an ensemble)."""
+    if fields.ndim == 4 and group == 1:
+        fields = fields.unsqueeze(1)
+    if not (fields.is_cuda and fields.ndim == 5 and fields.dtype == torch.float32 and fields.shape[1] == group):
+        raise ValueError(f"zonal_power: fp32 device fields [n, {group}, V, H, W] expected, got {fields.dtype} "
+                         f"{tuple(fields.shape)} on {fields.device}")
+    n, G, V, H, W = fields.shape
+    fields = fields.contiguous()
+    w_lat, twiddle = _spectrum_tables(W, lat, fields.device)
+    if w_lat.numel() != H:
+        raise ValueError(f"zonal_power: {w_lat.numel()} latitudes for {H} rows")
+    out = torch.empty(n, V, W // 2 + 1, dtype=torch.float64, device=fields.device)  # written completely by every call
+    check(lib().swiftk_zonal_power(fields.data_ptr(), w_lat.data_ptr(), twiddle.data_ptr(), out.data_ptr(), n, G, V, H, W,
+                                   torch.cuda.current_stream().cuda_stream), "swiftk_zonal_power")
+    return out
+
+
 def all_metrics(pred: torch.Tensor, y: torch.Tensor, vars: Sequence[str], lat, log_postfix: str) -> Dict[str, torch.Tensor]:
     B, N, V, H, W = pred.shape
     s = ensemble_sums(pred, y, lat).double()

@@ -19,7 +19,10 @@ run), ``--num-steps``,
 ``--dtype``, ``--synthetic`` (random-init weights + synthetic fields when no run directory
 exists), ``--metrics`` (ensemble RMSE / CRPS / spread-skill against the dataset's own fields,
 reduced per rank on the device and all-gathered: eval/metrics.py:39-134 without the round trip
-through the store) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
+through the store), ``--spectra`` (implies ``--metrics``; adds ``evaluation_spectra.npz`` beside evaluation_metrics.json:
+latitude-weighted zonal power spectra of the members, of the ensemble mean and of the verifying fields per lead step and
+variable, ``swiftk_zonal_power`` in fp64 on the device -- whether the members stay as sharp as the truth, which RMSE and CRPS
+cannot tell) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
 """
 from __future__ import annotations
 
@@ -65,6 +68,8 @@ parser.add_argument("--solver", type=str, default=None, choices=["scm", "2s", "d
 parser.add_argument("--num-steps", type=int, default=None, help="solver steps per forecast step (default: 1; an EDM run's "
                     "saved solver.num_steps)")
 parser.add_argument("--metrics", action="store_true", help="ensemble metrics vs the dataset's fields -> evaluation_metrics.json")
+parser.add_argument("--spectra", action="store_true", help="implies --metrics; zonal power spectra of the members, the ensemble "
+                    "mean and the verifying fields per lead step and variable -> evaluation_spectra.npz")
 
 
 def get_ckpt_num(fpath: str) -> int:
@@ -136,7 +141,8 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
         var_channels = zarrlite.variable_channels(list(dataset.variables))
     rank, world = dist.get_rank(), dist.get_world_size()
     n_ic = len(indices)
-    want_metrics = bool(getattr(args, "metrics", False))
+    want_spectra = bool(getattr(args, "spectra", False))
+    want_metrics = bool(getattr(args, "metrics", False)) or want_spectra
     batch = int(args.batch)
     if want_metrics:  # an IC's members must meet in one batch: whole ICs per rank and per batch
         batch = max(members, batch // members * members)
@@ -148,6 +154,7 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     interval = engine.interval
     done = 0
     metric_sums = {}  # IC position -> [steps, nv, 4] float64 (swiftk_ensemble_sums rows)
+    spectra_sum = [None]  # --spectra: [steps, nv, 3, K] float64 on the device, this rank's ICs added in IC order
     # Output streaming (the reference copies every step to the host synchronously, generate.py:129).
     from concurrent.futures import ThreadPoolExecutor
     writer = ThreadPoolExecutor(max_workers=1)
@@ -266,7 +273,11 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             slots = [b for b, (_, i) in enumerate(units) if i == ic]
             assert len(slots) == members and slots == list(range(slots[0], slots[0] + members))
             pred = dev_buf[1:, slots[0]:slots[0] + members].contiguous()       # [steps, members, nv, H, W]
-            metric_sums[ic] = ensemble_sums(pred, truth[k].to(pred.device, non_blocking=True), lat).double().cpu()
+            y = truth[k].to(pred.device, non_blocking=True)
+            metric_sums[ic] = ensemble_sums(pred, y, lat).double().cpu()
+            if want_spectra:
+                s = ic_spectra(pred, y, lat)
+                spectra_sum[0] = s if spectra_sum[0] is None else spectra_sum[0] + s
 
     reader = ThreadPoolExecutor(max_workers=1)
     loaders = ThreadPoolExecutor(max_workers=8)
@@ -313,7 +324,12 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
         os.close(store_fd)
     dist.log0(f"host side: {t_host[0]:.2f} s staging inputs, {t_host[1]:.2f} s writing outputs")
     if want_metrics:
-        return collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, device, os.path.dirname(ofile))
+        res = collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, device, os.path.dirname(ofile))
+        if want_spectra:
+            K = dataset.img_resolution[1] // 2 + 1
+            local = spectra_sum[0] if spectra_sum[0] is not None else torch.zeros(steps, nv, 3, K, dtype=torch.float64, device=device)
+            collect_spectra(local, n_ic, members, dataset.variables, interval, os.path.dirname(ofile))
+        return res
     return None
 
 
@@ -350,6 +366,46 @@ def collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, de
         json.dump(res, f, indent=1)
     dist.log0(f"ensemble metrics of {n_ic} ICs x {members} members gathered from {dist.get_world_size()} rank(s): {path}")
     return res
+
+
+def ic_spectra(pred, y, lat):
+    """One IC's zonal power spectra: pred [steps, members, nv, H, W] and truth y [steps, nv, H, W] (device, fp32) ->
+    [steps, nv, 3, K] fp64 on the device: the member spectra summed over the members, the spectrum of the ensemble mean, the
+    spectrum of the verifying fields."""
+    from .eval.metrics import zonal_power
+    steps, members, nv, H, W = pred.shape
+    member = zonal_power(pred.view(steps * members, nv, H, W), lat).view(steps, members, nv, -1).sum(1)
+    return torch.stack([member, zonal_power(pred, lat, group=members), zonal_power(y.contiguous(), lat)], 2)
+
+
+SPECTRA_FILE = "evaluation_spectra.npz"
+
+
+def collect_spectra(local, n_ic, members, variables, interval, odir):
+    """``local`` [steps, nv, 3, K] fp64: this rank's sums over its ICs (``ic_spectra`` rows).  One all-gather of these arrays (not
+    of per-IC rows: 64 ICs x 60 steps of them are 0.8 GB per rank), rank 0 adds them in rank order, divides by the number of
+    terms and writes ``evaluation_spectra.npz`` (plain arrays, no pickles): wavenumber [K], lead_hours [steps], variables [nv],
+    member / ensemble_mean / truth [steps, nv, K] (means over ICs and members / ICs / ICs), members, samples."""
+    if dist.collectives_active():
+        parts = [torch.empty_like(local) for _ in range(dist.get_world_size())]
+        tdist.all_gather(parts, local)
+    else:
+        parts = [local]
+    if dist.get_rank() != 0:
+        return None
+    total = parts[0].cpu().numpy().copy()
+    for p in parts[1:]:
+        total += p.cpu().numpy()
+    steps, nv, _, K = total.shape
+    arrays = dict(wavenumber=np.arange(K, dtype=np.int64), lead_hours=(np.arange(steps, dtype=np.int64) + 1) * int(interval),
+                  variables=np.array([str(v) for v in variables], dtype=np.str_),
+                  member=total[:, :, 0] / (n_ic * members), ensemble_mean=total[:, :, 1] / n_ic, truth=total[:, :, 2] / n_ic,
+                  members=np.int64(members), samples=np.int64(n_ic))
+    path = os.path.join(odir, SPECTRA_FILE)
+    np.savez(path, allow_pickle=False, **arrays)
+    dist.log0(f"zonal power spectra (--spectra) of {n_ic} ICs x {members} members, {K} wavenumbers, gathered from "
+              f"{dist.get_world_size()} rank(s): {path}")
+    return arrays
 
 
 def load_cfg(args) -> Cfg:
@@ -408,6 +464,8 @@ def main(args):
     dist.log0("Constructing network...")
     net, ckpt_basename = build_net(cfg, dataset, args, device)
 
+    if args.spectra:
+        args.metrics = True
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
         if args.dump == "none":
