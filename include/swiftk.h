@@ -597,6 +597,25 @@ int swiftk_sweep_sse(const float* xstd, int64_t x_batch_stride, const float* y, 
  * (SWIFTK_EALIGN). */
 int swiftk_zonal_power(const float* x, const double* w_lat, const double* twiddle, double* out, int n, int G, int V, int H, int W,
                        void* stream);
+/* Rank (Talagrand) histograms of an ensemble against the verifying fields (the calibration evidence of `generate --rank-hist`;
+ * it complements the spread-skill ratio of eval/metrics.py:108-134, which compares two grid averages and cannot tell a biased
+ * ensemble that is too wide, or one that is too narrow in the tropics and too wide elsewhere, from a calibrated one).
+ * pred [n, N, V, H, W] and y [n, V, H, W] fp32 contiguous (the layout of swiftk_ensemble_sums, n lead steps of one IC), w_lat [H]
+ * fp64 (cos(lat) / mean(cos(lat)), as for swiftk_zonal_power), out [n, V, N + 1] fp64.  At pixel (h, w) of plane (i, v) let
+ * b = #{m: x_m < y} and e = #{m: x_m == y} (IEEE comparisons: -0 ties with +0); the pixel adds w_lat[h] / (e + 1) to every bin r
+ * with b <= r <= b + e.  Without ties that is the usual rank; with ties the unit mass is spread evenly over the ranks the truth
+ * could take -- no random tie-break, no RNG -- so sum_r out[i,v,r] = W sum_h w_lat[h] and an all-equal plane fills every bin
+ * alike.  Inputs are assumed finite, as everywhere in the metrics: NaN is not detected (it compares false both ways: a NaN truth lands
+ * in bin 0, a NaN member counts as one above the truth).
+ * All counting is in exact integers, row by row (T_h[e][r]: the pixels of row h with tie size e whose range covers r); floating
+ * point enters in three places, all fp64: row[r] = sum over e ascending of T_h[e][r] / (e + 1), acc[r] += w_lat[h] * row[r]
+ * (product and sum rounded separately), rows added in ascending h.  One workgroup per (i, v) plane; no float atomics, no scratch
+ * buffer, and out is written completely by every call (no clearing).  The bits of a plane's row of out depend on (N, H, W), the
+ * weights and the plane's values only -- not on n, V, the plane's position in the batch or the rank.
+ * Refused before any launch: a null pointer or a non-positive size (SWIFTK_EINVAL); N > 64 or n V above 2^31 - 1
+ * (SWIFTK_ESHAPE); pred or y off a 4-byte boundary, w_lat or out off an 8-byte one (SWIFTK_EALIGN).  H and W are not restricted. */
+int swiftk_rank_histogram(const float* pred, const float* y, const double* w_lat, double* out, int n, int N, int V, int H, int W,
+                          void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
  * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host. */

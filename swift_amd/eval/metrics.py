@@ -69,6 +69,26 @@ def zonal_power(fields: torch.Tensor, lat, group: int = 1) -> torch.Tensor:
     return out
 
 
+def rank_histogram(pred: torch.Tensor, y: torch.Tensor, lat) -> torch.Tensor:
+    """Latitude-weighted rank (Talagrand) histograms (definition: include/swiftk.h, ``swiftk_rank_histogram``: a pixel with b
+    members below the truth and e equal to it adds w_lat[h] / (e + 1) to the bins b .. b + e, so a row sums to W sum(w_lat)).
+    pred [n, N, V, H, W], y [n, V, H, W], fp32 on the device -> [n, V, N + 1] fp64 on the device."""
+    if not (pred.is_cuda and y.is_cuda and pred.ndim == 5 and y.ndim == 4 and pred.dtype == torch.float32
+            and y.dtype == torch.float32 and y.device == pred.device
+            and tuple(y.shape) == (pred.shape[0],) + tuple(pred.shape[2:])):
+        raise ValueError(f"rank_histogram: fp32 device pred [n, N, V, H, W] and y [n, V, H, W] expected, got {pred.dtype} "
+                         f"{tuple(pred.shape)} on {pred.device} and {y.dtype} {tuple(y.shape)} on {y.device}")
+    n, N, V, H, W = pred.shape
+    pred, y = pred.contiguous(), y.contiguous()
+    w_lat, _ = _spectrum_tables(W, lat, pred.device)   # the fp64 weights of the spectra (the twiddle table rides along unused)
+    if w_lat.numel() != H:
+        raise ValueError(f"rank_histogram: {w_lat.numel()} latitudes for {H} rows")
+    out = torch.empty(n, V, N + 1, dtype=torch.float64, device=pred.device)  # written completely by every call
+    check(lib().swiftk_rank_histogram(pred.data_ptr(), y.data_ptr(), w_lat.data_ptr(), out.data_ptr(), n, N, V, H, W,
+                                      torch.cuda.current_stream().cuda_stream), "swiftk_rank_histogram")
+    return out
+
+
 def all_metrics(pred: torch.Tensor, y: torch.Tensor, vars: Sequence[str], lat, log_postfix: str) -> Dict[str, torch.Tensor]:
     B, N, V, H, W = pred.shape
     s = ensemble_sums(pred, y, lat).double()

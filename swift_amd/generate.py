@@ -22,7 +22,11 @@ reduced per rank on the device and all-gathered: eval/metrics.py:39-134 without 
 through the store), ``--spectra`` (implies ``--metrics``; adds ``evaluation_spectra.npz`` beside evaluation_metrics.json:
 latitude-weighted zonal power spectra of the members, of the ensemble mean and of the verifying fields per lead step and
 variable, ``swiftk_zonal_power`` in fp64 on the device -- whether the members stay as sharp as the truth, which RMSE and CRPS
-cannot tell) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
+cannot tell), ``--rank-hist`` (implies ``--metrics``; adds ``evaluation_rank_histogram.npz``: per lead step and variable the
+latitude-weighted frequency with which the verifying value takes each rank 0 .. members among the members, ties spread evenly,
+``swiftk_rank_histogram`` in exact integers and fp64 on the device -- flat is calibrated, U-shaped under-dispersive, dome-shaped
+over-dispersive, sloped biased, which one spread-skill number per variable cannot tell) and ``--gpus N`` (start the N ranks
+from a bare ``python -m`` call).
 """
 from __future__ import annotations
 
@@ -70,6 +74,8 @@ parser.add_argument("--num-steps", type=int, default=None, help="solver steps pe
 parser.add_argument("--metrics", action="store_true", help="ensemble metrics vs the dataset's fields -> evaluation_metrics.json")
 parser.add_argument("--spectra", action="store_true", help="implies --metrics; zonal power spectra of the members, the ensemble "
                     "mean and the verifying fields per lead step and variable -> evaluation_spectra.npz")
+parser.add_argument("--rank-hist", action="store_true", help="implies --metrics; rank (Talagrand) histogram of the verifying "
+                    "fields among the members per lead step and variable -> evaluation_rank_histogram.npz")
 
 
 def get_ckpt_num(fpath: str) -> int:
@@ -142,7 +148,8 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     rank, world = dist.get_rank(), dist.get_world_size()
     n_ic = len(indices)
     want_spectra = bool(getattr(args, "spectra", False))
-    want_metrics = bool(getattr(args, "metrics", False)) or want_spectra
+    want_rank_hist = bool(getattr(args, "rank_hist", False))
+    want_metrics = bool(getattr(args, "metrics", False)) or want_spectra or want_rank_hist
     batch = int(args.batch)
     if want_metrics:  # an IC's members must meet in one batch: whole ICs per rank and per batch
         batch = max(members, batch // members * members)
@@ -155,6 +162,7 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     done = 0
     metric_sums = {}  # IC position -> [steps, nv, 4] float64 (swiftk_ensemble_sums rows)
     spectra_sum = [None]  # --spectra: [steps, nv, 3, K] float64 on the device, this rank's ICs added in IC order
+    rank_hist_sum = [None]  # --rank-hist: [steps, nv, members + 1] float64 on the device, this rank's ICs added in IC order
     # Output streaming (the reference copies every step to the host synchronously, generate.py:129).
     from concurrent.futures import ThreadPoolExecutor
     writer = ThreadPoolExecutor(max_workers=1)
@@ -278,6 +286,9 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             if want_spectra:
                 s = ic_spectra(pred, y, lat)
                 spectra_sum[0] = s if spectra_sum[0] is None else spectra_sum[0] + s
+            if want_rank_hist:
+                r = ic_rank_histogram(pred, y, lat)
+                rank_hist_sum[0] = r if rank_hist_sum[0] is None else rank_hist_sum[0] + r
 
     reader = ThreadPoolExecutor(max_workers=1)
     loaders = ThreadPoolExecutor(max_workers=8)
@@ -329,6 +340,12 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             K = dataset.img_resolution[1] // 2 + 1
             local = spectra_sum[0] if spectra_sum[0] is not None else torch.zeros(steps, nv, 3, K, dtype=torch.float64, device=device)
             collect_spectra(local, n_ic, members, dataset.variables, interval, os.path.dirname(ofile))
+        if want_rank_hist:
+            w = np.cos(np.deg2rad(np.asarray(dataset.get_lat_lon()[0], dtype=np.float64)))
+            norm = float(dataset.img_resolution[1]) * float((w / w.mean()).sum())   # what one plane's bins sum to: W sum(w_lat)
+            local = rank_hist_sum[0] if rank_hist_sum[0] is not None else torch.zeros(steps, nv, members + 1, dtype=torch.float64,
+                                                                                      device=device)
+            collect_rank_histogram(local, n_ic, members, dataset.variables, interval, norm, os.path.dirname(ofile))
         return res
     return None
 
@@ -408,6 +425,44 @@ def collect_spectra(local, n_ic, members, variables, interval, odir):
     return arrays
 
 
+def ic_rank_histogram(pred, y, lat):
+    """One IC's rank histograms: pred [steps, members, nv, H, W] and truth y [steps, nv, H, W] (device, fp32) ->
+    [steps, nv, members + 1] fp64 on the device, each row summing to W sum(w_lat)."""
+    from .eval.metrics import rank_histogram
+    return rank_histogram(pred, y.contiguous(), lat)
+
+
+RANK_HIST_FILE = "evaluation_rank_histogram.npz"
+
+
+def collect_rank_histogram(local, n_ic, members, variables, interval, norm, odir):
+    """``local`` [steps, nv, members + 1] fp64: this rank's sums over its ICs (``ic_rank_histogram`` rows).  One all-gather of
+    these arrays (never of per-IC rows), rank 0 adds them in rank order, divides by ``n_ic * norm`` (``norm`` = W sum(w_lat), what
+    one plane's bins sum to) so that each (lead, variable) row sums to 1, and writes ``evaluation_rank_histogram.npz`` (plain
+    arrays, no pickles): rank [members + 1], lead_hours [steps], variables [nv], frequency [steps, nv, members + 1], members,
+    samples."""
+    if dist.collectives_active():
+        parts = [torch.empty_like(local) for _ in range(dist.get_world_size())]
+        tdist.all_gather(parts, local)
+    else:
+        parts = [local]
+    if dist.get_rank() != 0:
+        return None
+    total = parts[0].cpu().numpy().copy()
+    for p in parts[1:]:
+        total += p.cpu().numpy()
+    steps, nv, bins = total.shape
+    assert bins == members + 1
+    arrays = dict(rank=np.arange(bins, dtype=np.int64), lead_hours=(np.arange(steps, dtype=np.int64) + 1) * int(interval),
+                  variables=np.array([str(v) for v in variables], dtype=np.str_), frequency=total / (n_ic * float(norm)),
+                  members=np.int64(members), samples=np.int64(n_ic))
+    path = os.path.join(odir, RANK_HIST_FILE)
+    np.savez(path, allow_pickle=False, **arrays)
+    dist.log0(f"rank histograms (--rank-hist) of {n_ic} ICs x {members} members, {bins} ranks, gathered from "
+              f"{dist.get_world_size()} rank(s): {path}")
+    return arrays
+
+
 def load_cfg(args) -> Cfg:
     """The run's saved composed config (generate.py:161), or the synthetic one when ``--synthetic`` names no run directory."""
     if args.synthetic and not os.path.exists(os.path.join(args.input, ".hydra", "config.yaml")):
@@ -464,7 +519,7 @@ def main(args):
     dist.log0("Constructing network...")
     net, ckpt_basename = build_net(cfg, dataset, args, device)
 
-    if args.spectra:
+    if args.spectra or args.rank_hist:
         args.metrics = True
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
