@@ -387,6 +387,8 @@ class OracleNet:
         if self.emulate_bf16:
             kw.setdefault("emulate_bf16", self.emulate_bf16)
         aux = process_auxiliary(auxiliary, self.auxiliary_dim, x.size(0), x.device)
+        if aux is not None:
+            aux = aux.to(x.dtype)  # (a no-op in fp32; lets the whole oracle run in fp64 when state and inputs are fp64)
         arg = x
         if condition is not None and self.condition_channels > 0:
             arg = torch.cat([arg, condition], dim=1)
