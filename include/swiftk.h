@@ -616,6 +616,30 @@ int swiftk_zonal_power(const float* x, const double* w_lat, const double* twiddl
  * (SWIFTK_ESHAPE); pred or y off a 4-byte boundary, w_lat or out off an 8-byte one (SWIFTK_EALIGN).  H and W are not restricted. */
 int swiftk_rank_histogram(const float* pred, const float* y, const double* w_lat, double* out, int n, int N, int V, int H, int W,
                           void* stream);
+/* Per-pixel summary of an ensemble: mean, spread and quantiles over the members (the product of `generate --summary`; the
+ * reference has none -- its users dump every member and reduce the store offline).
+ * pred [n, N, V, H, W] fp32 contiguous (the layout of swiftk_ensemble_sums and swiftk_rank_histogram, n lead steps of one IC),
+ * out [n, 2 + Q, V, H, W] fp32: statistic 0 the mean, 1 the spread, 2 + j quantile j.  q_lo [Q] int32 and q_frac [Q] fp64 on the
+ * device hold floor(q (N - 1)) and the fraction left over, computed by the host (numpy's default `linear` method).
+ * For the members x_0 .. x_{N-1} of a pixel, every operation below one correctly rounded fp64 operation, never fused:
+ *   mean:   s = the members widened to fp64 and added in member order; mean64 = s / N; out = (float) mean64.
+ *   spread: d_m = x_m - mean64; v = the sum over m in member order of d_m * d_m (product and sum rounded separately);
+ *           out = (float) sqrt(v / (N - 1)), the unbiased standard deviation (torch.var of eval/metrics.py:124, per pixel).
+ *   quantile j: with x_(0) <= .. <= x_(N-1) the members in ascending order, a = x_(lo), b = x_(min(lo + 1, N - 1)), lo = q_lo[j]
+ *           clamped into [0, N - 1] (the table is read on the device, so it cannot be checked before the launch), g = q_frac[j]:
+ *           out = (float)(a + g * (b - a)), difference, product and sum each rounded, in that order.  g == 0 gives a exactly, so
+ *           min, max and every quantile that falls on a member are selections.
+ * Identical members give mean = the member and spread = 0.0 exactly (N x is exact in fp64 for N <= 64).  Comparisons are IEEE:
+ * -0 ties with +0 (either may stand for the other in a quantile).  Inputs are assumed finite, as everywhere in the metrics: NaN is
+ * not detected.  fp64 because fp32 fails here: twelve members at 280 K under a spread of 1e-2 K lose the spread to hundreds of
+ * half-ulps and more in an fp32 two-pass formula, and an fp32 mean of three members already misses its correctly rounded value.
+ * A thread owns a pixel; no atomics, no scratch buffer, and out is written completely by every call (no clearing).  A pixel's
+ * outputs depend on its N values and the table only -- not on n, V, the pixel's position in the batch or the rank.
+ * Refused before any launch: a null pointer (the table pointers only when Q > 0) or a non-positive n, N, V, H or W
+ * (SWIFTK_EINVAL); N < 2 or N > 64, Q < 0 or Q > 16, n V above 2^31 - 1 (SWIFTK_ESHAPE); pred, out or q_lo off a 4-byte boundary,
+ * q_frac off an 8-byte one (SWIFTK_EALIGN).  Q = 0 is legal (mean and spread only).  H and W are not restricted. */
+int swiftk_ensemble_summary(const float* pred, const int* q_lo, const double* q_frac, float* out, int n, int N, int V, int H, int W,
+                            int Q, void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
  * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host. */

@@ -89,6 +89,51 @@ def rank_histogram(pred: torch.Tensor, y: torch.Tensor, lat) -> torch.Tensor:
     return out
 
 
+MAX_QUANTILES = 16  # what swiftk_ensemble_summary takes in one call
+
+
+def quantile_table(quantiles, N: int):
+    """Host side of the quantiles of ``ensemble_summary``: for each q in [0, 1] the position p = q (N - 1) among the N sorted
+    members, in fp64, as (lo int32 [Q], frac float64 [Q]) with lo = floor(p), frac = p - lo (numpy's default ``linear`` method);
+    q = 1 gives (N - 1, 0.0).  ``ValueError`` for a q outside [0, 1] or not finite, for more than 16 quantiles, for N < 2."""
+    q = np.asarray(list(quantiles), dtype=np.float64).reshape(-1)
+    if int(N) < 2:
+        raise ValueError(f"quantile_table: at least 2 members, got {N}")
+    if q.size > MAX_QUANTILES:
+        raise ValueError(f"quantile_table: at most {MAX_QUANTILES} quantiles, got {q.size}")
+    if not np.all(np.isfinite(q)) or np.any(q < 0.0) or np.any(q > 1.0):
+        raise ValueError(f"quantile_table: quantiles must be finite numbers in [0, 1], got {q.tolist()}")
+    p = q * np.float64(int(N) - 1)
+    lo = np.floor(p)
+    return lo.astype(np.int32), p - lo
+
+
+_QUANTILE_TABLES: dict = {}  # (quantiles, N, device) -> (lo int32 [Q], frac fp64 [Q]) on the device
+
+
+def ensemble_summary(pred: torch.Tensor, quantiles=(0.1, 0.5, 0.9)) -> torch.Tensor:
+    """Per-pixel mean, spread (unbiased standard deviation) and quantiles over the members (definition: include/swiftk.h,
+    ``swiftk_ensemble_summary``: fp64 in member order, quantiles as selections plus one interpolation).  pred [n, N, V, H, W] fp32
+    on the device -> [n, 2 + Q, V, H, W] fp32 on the device: statistic 0 the mean, 1 the spread, 2 + j quantile j."""
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda and pred.ndim == 5 and pred.dtype == torch.float32
+            and 2 <= pred.shape[1] <= 64 and pred.numel() > 0):
+        raise ValueError(f"ensemble_summary: fp32 device pred [n, N, V, H, W] with 2 <= N <= 64 expected, got "
+                         f"{getattr(pred, 'dtype', type(pred))} {tuple(getattr(pred, 'shape', ()))} on {getattr(pred, 'device', None)}")
+    n, N, V, H, W = pred.shape
+    key = (tuple(float(q) for q in quantiles), N, str(pred.device))
+    if key not in _QUANTILE_TABLES:
+        lo, frac = quantile_table(key[0], N)
+        _QUANTILE_TABLES[key] = (torch.from_numpy(lo).to(pred.device), torch.from_numpy(frac).to(pred.device))
+    lo, frac = _QUANTILE_TABLES[key]
+    Q = len(key[0])
+    pred = pred.contiguous()
+    out = torch.empty(n, 2 + Q, V, H, W, dtype=torch.float32, device=pred.device)  # written completely by every call
+    check(lib().swiftk_ensemble_summary(pred.data_ptr(), lo.data_ptr() if Q else None, frac.data_ptr() if Q else None,
+                                        out.data_ptr(), n, N, V, H, W, Q, torch.cuda.current_stream().cuda_stream),
+          "swiftk_ensemble_summary")
+    return out
+
+
 def all_metrics(pred: torch.Tensor, y: torch.Tensor, vars: Sequence[str], lat, log_postfix: str) -> Dict[str, torch.Tensor]:
     B, N, V, H, W = pred.shape
     s = ensemble_sums(pred, y, lat).double()

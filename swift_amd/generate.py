@@ -25,8 +25,14 @@ variable, ``swiftk_zonal_power`` in fp64 on the device -- whether the members st
 cannot tell), ``--rank-hist`` (implies ``--metrics``; adds ``evaluation_rank_histogram.npz``: per lead step and variable the
 latitude-weighted frequency with which the verifying value takes each rank 0 .. members among the members, ties spread evenly,
 ``swiftk_rank_histogram`` in exact integers and fp64 on the device -- flat is calibrated, U-shaped under-dispersive, dome-shaped
-over-dispersive, sloped biased, which one spread-skill number per variable cannot tell) and ``--gpus N`` (start the N ranks
-from a bare ``python -m`` call).
+over-dispersive, sloped biased, which one spread-skill number per variable cannot tell), ``--summary [--quantiles q ...]``
+(writes ``<output name>-summary.zarr`` beside the other outputs: per IC, lead step (lead 0 included), variable and grid point the
+ensemble mean, the spread and the quantiles, default 0.1 0.5 0.9 -- the forecast store's structure with a ``statistic`` dimension
+where ``number`` stands; ``swiftk_ensemble_summary`` in fp64 on the device, one call per IC on the members the device already
+holds, so the raw trajectories never leave it on this flag's account: what a forecaster reads out of an ensemble, at
+(2 + quantiles) / members of the raw store's size; it needs an IC's members in one batch, like the metrics, but does not imply
+them and loads no verifying fields: ``--dump none --summary`` is a complete job) and ``--gpus N`` (start the N ranks from a
+bare ``python -m`` call).
 """
 from __future__ import annotations
 
@@ -76,6 +82,10 @@ parser.add_argument("--spectra", action="store_true", help="implies --metrics; z
                     "mean and the verifying fields per lead step and variable -> evaluation_spectra.npz")
 parser.add_argument("--rank-hist", action="store_true", help="implies --metrics; rank (Talagrand) histogram of the verifying "
                     "fields among the members per lead step and variable -> evaluation_rank_histogram.npz")
+parser.add_argument("--summary", action="store_true", help="per IC, lead step, variable and grid point the ensemble mean, spread "
+                    "and quantiles -> <output name>-summary.zarr (does not imply --metrics)")
+parser.add_argument("--quantiles", type=float, nargs="+", default=[0.1, 0.5, 0.9], help="quantiles of --summary, each in [0, 1], "
+                    "at most 16 (default: 0.1 0.5 0.9)")
 
 
 def get_ckpt_num(fpath: str) -> int:
@@ -150,8 +160,9 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     want_spectra = bool(getattr(args, "spectra", False))
     want_rank_hist = bool(getattr(args, "rank_hist", False))
     want_metrics = bool(getattr(args, "metrics", False)) or want_spectra or want_rank_hist
+    want_summary = bool(getattr(args, "summary", False))
     batch = int(args.batch)
-    if want_metrics:  # an IC's members must meet in one batch: whole ICs per rank and per batch
+    if want_metrics or want_summary:  # an IC's members must meet in one batch: whole ICs per rank and per batch
         batch = max(members, batch // members * members)
         ic_range = dist.shard_units(n_ic, rank, world)
         mine = range(ic_range.start * members, ic_range.stop * members)
@@ -270,6 +281,46 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
         t_host[0] += time.time() - t1
         return units, X0, forc, truth
 
+    # --summary: the [steps + 1, 2 + Q, nv, H, W] result of an IC stays on the device until the summary thread has taken it --
+    # through one pinned buffer on a stream of its own -- and written its 2 + Q chunk files per variable; the rollout loop never
+    # waits for a copy, only, one batch's worth of ICs later, for the files (back-pressure when the store is slower than the GPU)
+    summary_file = summary_path(ofile)
+    summary_writer = ThreadPoolExecutor(max_workers=1) if want_summary else None
+    summary_stream = torch.cuda.Stream(device=device) if want_summary and on_gpu else None
+    summary_host, summary_pending = [None], []
+
+    def flush_summary(out_dev, ready, ic):
+        with torch.cuda.device(device):
+            if summary_host[0] is None:
+                summary_host[0] = torch.empty(out_dev.shape, dtype=torch.float32, pin_memory=True)
+            with torch.cuda.stream(summary_stream):
+                summary_stream.wait_event(ready)
+                summary_host[0].copy_(out_dev, non_blocking=True)
+            summary_stream.synchronize()
+        del out_dev
+        t1 = time.time()
+        h = summary_host[0].numpy()  # [steps + 1, 2 + Q, nv, H, W]
+        list(loaders.map(lambda k: zarrlite.write_unit(summary_file, summary_channels, ic, k, h[:, k]), range(h.shape[1])))
+        t_host[1] += time.time() - t1
+
+    def batch_summary(units, dev_buf):
+        """Per IC of the batch: swiftk_ensemble_summary of its members at every lead step, lead 0 included."""
+        from .eval.metrics import ensemble_summary
+        uniq = sorted(set(ic for _, ic in units))
+        for ic in uniq:
+            slots = [b for b, (_, i) in enumerate(units) if i == ic]
+            assert len(slots) == members and slots == list(range(slots[0], slots[0] + members))
+            out = ensemble_summary(dev_buf[:, slots[0]:slots[0] + members], args.quantiles)
+            ready = torch.cuda.Event()
+            ready.record()
+            while len(summary_pending) >= len(uniq):
+                summary_pending.pop(0).result()
+            summary_pending.append(summary_writer.submit(flush_summary, out, ready, ic))
+
+    if want_summary:
+        from .utils import zarrlite
+        summary_channels = zarrlite.variable_channels(list(dataset.variables))
+
     def batch_metrics(units, dev_buf, truth):
         """Per IC of the batch: swiftk_ensemble_sums of its members against the verifying fields at every lead step."""
         from .eval.metrics import ensemble_sums
@@ -306,6 +357,8 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
         dev_buf = traj.transpose(0, 1)      # the contiguous step-major buffer behind it
         if want_metrics:
             batch_metrics(units, dev_buf, truth)
+        if want_summary:
+            batch_summary(units, dev_buf)
         if on_gpu:
             dev_buf.record_stream(copy_stream)  # its last slabs may still be on their way to the host
             done += len(units)
@@ -327,6 +380,10 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     for f in ring_busy:
         if f is not None:
             f.result()
+    for f in summary_pending:
+        f.result()
+    if summary_writer is not None:
+        summary_writer.shutdown()
     writer.shutdown()
     reader.shutdown()
     loaders.shutdown()
@@ -348,6 +405,27 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             collect_rank_histogram(local, n_ic, members, dataset.variables, interval, norm, os.path.dirname(ofile))
         return res
     return None
+
+
+def summary_path(ofile: str) -> str:
+    """``<output name>-summary.zarr`` beside the job's other outputs (``ofile``: the raw store's name, whatever ``--dump``)."""
+    return os.path.splitext(ofile)[0] + "-summary.zarr"
+
+
+def create_empty_summary(sfile, dataset, indices, members, steps, interval, quantiles):
+    from .utils import zarrlite
+    lat, lon = dataset.get_lat_lon()
+    times = np.array([dataset.get_time(int(i)) for i in indices], dtype="datetime64[ns]")
+    zarrlite.create_summary_store(sfile, list(dataset.variables), times, lat, lon, members, steps, quantiles, interval=interval)
+
+
+def check_summary_args(args):
+    """``--summary`` / ``--quantiles`` checked on the host (``ValueError``), before any rank is started or the GPU is touched."""
+    if getattr(args, "summary", False):
+        from .eval.metrics import quantile_table
+        if not 2 <= args.members <= 64:
+            raise ValueError(f"--summary takes the statistics over 2 .. 64 members, got --members {args.members}")
+        quantile_table(args.quantiles, args.members)
 
 
 def collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, device, odir):
@@ -505,6 +583,7 @@ def build_net(cfg, dataset, args, device):
 
 
 def main(args):
+    check_summary_args(args)
     cfg = load_cfg(args)
     solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
     dist.setup_torch(backend=cfg.system.torch.backend)
@@ -527,7 +606,7 @@ def main(args):
             args.metrics = True
             dist.log0(f"{dist.get_world_size()} ranks and no --dump given: writing the ensemble metrics only (--dump none --metrics); raw "
                       "trajectories stream at 3.4 GB/s per rank -- pass --dump zarr / numpy to get them")
-    if args.dump == "none" and not args.metrics:
+    if args.dump == "none" and not args.metrics and not args.summary:
         raise ValueError("--dump none writes nothing but the metrics: add --metrics")
     odir = os.path.join(args.input, "output", ckpt_basename)
     dist.run_on_rank0(os.makedirs, odir, exist_ok=True)
@@ -541,6 +620,10 @@ def main(args):
     else:  # zarr (the reference's default, generate.py:41-43)
         ofile = os.path.join(odir, f"{filename}.zarr")
         dist.run_on_rank0(create_empty_zarr, ofile, dataset, indices, args.members, args.steps, args.interval)
+
+    if args.summary:
+        dist.run_on_rank0(create_empty_summary, summary_path(ofile), dataset, indices, args.members, args.steps, args.interval,
+                          args.quantiles)
 
     engine = RolloutEngine(net, dataset, interval=args.interval, solver=solver,
                            denoise_dtype=DENOISE_DTYPES[args.dtype],
@@ -557,13 +640,20 @@ def main(args):
     if args.dump == "zarr" and dist.get_rank() == 0:  # generate.py:281-285
         from .utils import zarrlite
         zarrlite.consolidate(ofile)
+    if args.summary and dist.get_rank() == 0:  # (after the barrier: every rank's chunk files are in place)
+        from .utils import zarrlite
+        zarrlite.consolidate(summary_path(ofile))
+        dist.log0(f"ensemble summary (--summary) of {len(indices)} ICs x {args.members} members, statistics "
+                  f"{', '.join(zarrlite.statistic_names(args.quantiles))} at {args.steps + 1} lead steps: {summary_path(ofile)}")
     if tdist.is_initialized():
         tdist.destroy_process_group()
-    dist.log0(f"Output saved to: {ofile if args.dump != 'none' else os.path.join(odir, 'evaluation_metrics.json')}")
+    dist.log0(f"Output saved to: "
+              f"{ofile if args.dump != 'none' else os.path.join(odir, 'evaluation_metrics.json') if args.metrics else summary_path(ofile)}")
     return ofile
 
 
 if __name__ == "__main__":
     _args = parser.parse_args()
+    check_summary_args(_args)
     dist.maybe_launch_ranks(_args.gpus, "swift_amd.generate")  # before anything touches the GPU; returns in the ranks
     main(_args)

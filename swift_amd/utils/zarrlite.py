@@ -120,9 +120,12 @@ def consolidate(root: str) -> None:
 
 
 def create_forecast_store(ofile: str, variables: Sequence[str], times: np.ndarray, lat: np.ndarray, lon: np.ndarray, members: int,
-                          steps: int, interval: int = 6, batch: int = 1) -> Dict[str, List[int]]:
-    """Empty forecast store with the reference's structure (utils/io.py:161-235); returns {variable: channel indices}."""
-    create_group(ofile)
+                          steps: int, interval: int = 6, batch: int = 1, member_dim: str = "number",
+                          attrs: Optional[dict] = None) -> Dict[str, List[int]]:
+    """Empty forecast store with the reference's structure (utils/io.py:161-235); returns {variable: channel indices}.
+    ``member_dim`` names the second dimension and its index coordinate (``create_summary_store`` puts ``statistic`` there),
+    ``attrs`` are the group's attributes."""
+    create_group(ofile, attrs)
     n = len(times)
     t_ns = np.asarray(times, dtype="datetime64[ns]").astype(np.int64)
     write_full(ofile, "time", t_ns, ["time"], {"units": "nanoseconds since 1970-01-01", "calendar": "proleptic_gregorian"})
@@ -130,7 +133,7 @@ def create_forecast_store(ofile: str, variables: Sequence[str], times: np.ndarra
     write_full(ofile, "prediction_timedelta", td, ["prediction_timedelta"], {"units": "nanoseconds", "dtype": "timedelta64[ns]"})
     write_full(ofile, "latitude", np.asarray(lat, np.float32), ["latitude"])
     write_full(ofile, "longitude", np.asarray(lon, np.float32), ["longitude"])
-    write_full(ofile, "number", np.arange(members, dtype=np.int64), ["number"])
+    write_full(ofile, member_dim, np.arange(members, dtype=np.int64), [member_dim])
     comp = compress_variables(variables)
     if any(len(lv) for lv in comp.values()):
         write_full(ofile, "level", np.arange(max(len(lv) for lv in comp.values()), dtype=np.int64), ["level"])
@@ -138,12 +141,29 @@ def create_forecast_store(ofile: str, variables: Sequence[str], times: np.ndarra
     for var, levels in comp.items():
         if levels:
             shape, chunks = (n, members, steps + 1, len(levels), n_lat, n_lon), (batch, 1, steps + 1, len(levels), n_lat, n_lon)
-            dims = ["time", "number", "prediction_timedelta", "level", "latitude", "longitude"]
+            dims = ["time", member_dim, "prediction_timedelta", "level", "latitude", "longitude"]
         else:
             shape, chunks = (n, members, steps + 1, n_lat, n_lon), (batch, 1, steps + 1, n_lat, n_lon)
-            dims = ["time", "number", "prediction_timedelta", "latitude", "longitude"]
+            dims = ["time", member_dim, "prediction_timedelta", "latitude", "longitude"]
         create_array(ofile, var, shape, chunks, np.float32, dims, fill_value=0.0)
     return variable_channels(variables)
+
+
+def statistic_names(quantiles: Sequence[float]) -> List[str]:
+    """Names of the statistics of a summary store, in the order of its ``statistic`` dimension: mean, spread, q<quantile> ..."""
+    return ["mean", "spread"] + [f"q{float(q):g}" for q in quantiles]
+
+
+def create_summary_store(ofile: str, variables: Sequence[str], times: np.ndarray, lat: np.ndarray, lon: np.ndarray, members: int,
+                         steps: int, quantiles: Sequence[float], interval: int = 6) -> Dict[str, List[int]]:
+    """Empty store of the per-pixel ensemble summary (``generate --summary``): the forecast store's structure with a ``statistic``
+    dimension of length 2 + Q (mean, spread, the quantiles; int64 index coordinate) where ``number`` stands, one uncompressed chunk
+    per (initial condition, statistic) and variable -- ``write_unit`` fills it with the statistic's index in the member's place.
+    Group attributes: ``statistics`` (their names in order), ``quantiles``, ``members`` (the ensemble size they were taken over)."""
+    names = statistic_names(quantiles)
+    return create_forecast_store(ofile, variables, times, lat, lon, len(names), steps, interval=interval, batch=1,
+                                 member_dim="statistic",
+                                 attrs={"statistics": names, "quantiles": [float(q) for q in quantiles], "members": int(members)})
 
 
 def write_unit(ofile: str, var_channels: Dict[str, List[int]], sample: int, member: int, traj: np.ndarray) -> None:
