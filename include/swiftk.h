@@ -642,7 +642,10 @@ int swiftk_ensemble_summary(const float* pred, const int* q_lo, const double* q_
                             int Q, void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
- * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host. */
+ * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host.
+ * fp32 terms added into out with fp32 atomics; the ensemble mean and the variance are taken about the first member
+ * (d_n = x_n - x_0), so their roundings scale with the member spread and not with the field's offset (280 K, 2e5 m^2/s^2),
+ * and members that all agree give a spread term and a variance of exactly 0. */
 int swiftk_ensemble_sums(const float* pred, const float* y, const float* w_lat, float* out, int B, int N, int V, int H, int W,
                          void* stream);
 /* Almost-fair CRPS over m members (loss.py:343-371,445): *loss += 1/(B H W) sum w_var[c] w_lat[h] crps; dpreds optional. */

@@ -519,7 +519,8 @@ def test_ensemble_sums(dev, N):
     pred, y = br.rnd((B, N, V, H, W), 60 + N), br.rnd((B, V, H, W), 61)
     w = omet._w(np.linspace(-80, 80, H), y)
     out = torch.zeros(B * V * 4, device=dev)
-    assert L().swiftk_ensemble_sums(pred.to(dev).data_ptr(), y.to(dev).data_ptr(), w.to(dev).data_ptr(), out.data_ptr(), B, N, V, H, W, s()) == 0
+    pd, yd, wd = pred.to(dev), y.to(dev), w.to(dev)   # (named: a temporary's block returns to the allocator once data_ptr() has been taken)
+    assert L().swiftk_ensemble_sums(pd.data_ptr(), yd.data_ptr(), wd.data_ptr(), out.data_ptr(), B, N, V, H, W, s()) == 0
     torch.cuda.synchronize()
     ref = br.ensemble_sums(pred, y, w)
     e = ((out.cpu().double().view(B, V, 4) - ref).abs() / ref.abs()).amax((0, 1))
