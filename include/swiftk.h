@@ -640,6 +640,32 @@ int swiftk_rank_histogram(const float* pred, const float* y, const double* w_lat
  * q_frac off an 8-byte one (SWIFTK_EALIGN).  Q = 0 is legal (mean and spread only).  H and W are not restricted. */
 int swiftk_ensemble_summary(const float* pred, const int* q_lo, const double* q_frac, float* out, int n, int N, int V, int H, int W,
                             int Q, void* stream);
+/* Per-grid-point verification terms of an ensemble against the verifying fields, written or added into a resident buffer: the
+ * maps of `generate --maps` (bias, MSE, CRPS and spread at every pixel, accumulated over initial conditions; every other
+ * verifying product is a whole-grid average and cannot say where a forecast is good).  The reference has none.
+ * pred [n, N, V, H, W] and y [n, V, H, W] fp32 contiguous (the layout of swiftk_rank_histogram, n lead steps of one IC),
+ * acc [n, 4, V, H, W] fp64: statistic 0 bias, 1 mse, 2 crps, 3 variance.
+ * For a pixel with members x_0 .. x_{N-1} and truth y, all widened to fp64, every operation below one correctly rounded fp64
+ * operation, never fused:
+ *   bias:     s = the members added in member order; mean = s / N; e = mean - y; term = e.
+ *   mse:      term = e * e.
+ *   crps:     a = the sum over m in member order of |x_m - y|; p = the sum over m < m' of |x_m - x_m'|, m ascending in the outer
+ *             loop, m' ascending in the inner one; term = a / N - p / (double)(N (N - 1)): the fair CRPS of eval/metrics.py:68-105,
+ *             per pixel.
+ *   variance: d_m = x_m - mean; v = the sum over m in member order of d_m * d_m (product and sum rounded separately);
+ *             term = v / (N - 1) (torch.var of eval/metrics.py:124, per pixel).
+ * Then acc = accumulate ? acc + term : term, one rounded add.  With accumulate == 0 the buffer is written completely and never
+ * read: the caller clears nothing.  Identical members give p = 0 and variance = 0 exactly.  Inputs are assumed finite, as
+ * everywhere in the metrics: NaN is not detected.  fp64 because fp32 fails here: at 280 K under a spread of 1e-2 K the variance,
+ * and the difference a / N - p / (N (N - 1)), are lost in fp32.
+ * A thread owns pixels, their members in registers (one kernel per multiple of 4 members); every element of acc belongs to
+ * exactly one thread: no atomics, no scratch buffer.  A pixel's four terms depend on its N + 1 values only -- not on n, V, the
+ * pixel's position in the batch or the rank.
+ * Refused before any launch: a null pointer, a non-positive n, N, V, H or W, accumulate outside {0, 1} (SWIFTK_EINVAL); N < 2 or
+ * N > 64, n V above 2^31 - 1 (SWIFTK_ESHAPE); pred or y off a 4-byte boundary, acc off an 8-byte one (SWIFTK_EALIGN).  H and W
+ * are not restricted. */
+int swiftk_ensemble_maps(const float* pred, const float* y, double* acc, int n, int N, int V, int H, int W, int accumulate,
+                         void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
  * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host.

@@ -134,6 +134,52 @@ def ensemble_summary(pred: torch.Tensor, quantiles=(0.1, 0.5, 0.9)) -> torch.Ten
     return out
 
 
+MAP_STATISTICS = ["bias", "mse", "crps", "variance"]  # the statistic axis of ensemble_maps, in order
+
+
+def ensemble_maps(pred: torch.Tensor, y: torch.Tensor, acc: torch.Tensor = None) -> torch.Tensor:
+    """Per-pixel bias, squared error, fair CRPS and member variance of an ensemble against the verifying fields (definition:
+    include/swiftk.h, ``swiftk_ensemble_maps``: fp64 in member order, nothing fused).  pred [n, N, V, H, W] and y [n, V, H, W],
+    fp32 on the device, 2 <= N <= 64 -> [n, 4, V, H, W] fp64 on the device, the statistics in the order of ``MAP_STATISTICS``.
+    Without ``acc`` the result is a new buffer, written completely; with ``acc`` (such a buffer, contiguous) the terms are added
+    to it in place, one rounded add each, and ``acc`` is returned: the sum over initial conditions that ``generate --maps`` keeps."""
+    if not (isinstance(pred, torch.Tensor) and isinstance(y, torch.Tensor) and pred.is_cuda and y.is_cuda and pred.ndim == 5
+            and y.ndim == 4 and pred.dtype == torch.float32 and y.dtype == torch.float32 and y.device == pred.device
+            and tuple(y.shape) == (pred.shape[0],) + tuple(pred.shape[2:]) and 2 <= pred.shape[1] <= 64 and pred.numel() > 0):
+        raise ValueError(f"ensemble_maps: fp32 device pred [n, N, V, H, W] with 2 <= N <= 64 and y [n, V, H, W] expected, got "
+                         f"{getattr(pred, 'dtype', type(pred))} {tuple(getattr(pred, 'shape', ()))} on {getattr(pred, 'device', None)} "
+                         f"and {getattr(y, 'dtype', type(y))} {tuple(getattr(y, 'shape', ()))} on {getattr(y, 'device', None)}")
+    n, N, V, H, W = pred.shape
+    if acc is not None and not (isinstance(acc, torch.Tensor) and acc.dtype == torch.float64 and acc.device == pred.device
+                                and tuple(acc.shape) == (n, 4, V, H, W) and acc.is_contiguous()):
+        raise ValueError(f"ensemble_maps: acc must be a contiguous fp64 [{n}, 4, {V}, {H}, {W}] buffer on {pred.device}, got "
+                         f"{getattr(acc, 'dtype', type(acc))} {tuple(getattr(acc, 'shape', ()))} on {getattr(acc, 'device', None)}")
+    pred, y = pred.contiguous(), y.contiguous()
+    accumulate = int(acc is not None)
+    if acc is None:
+        acc = torch.empty(n, 4, V, H, W, dtype=torch.float64, device=pred.device)  # written completely by the call
+    check(lib().swiftk_ensemble_maps(pred.data_ptr(), y.data_ptr(), acc.data_ptr(), n, N, V, H, W, accumulate,
+                                     torch.cuda.current_stream().cuda_stream), "swiftk_ensemble_maps")
+    return acc
+
+
+def region_means(maps: np.ndarray, lat) -> Dict[str, np.ndarray]:
+    """Latitude-weighted regional means of maps [..., H, W] (fp64) -> {region: [...]}: weights cos(lat), normalised over the
+    region's rows.  Regions (the WeatherBench2 bands): ``global``, ``tropics`` (|lat| <= 20), ``n_extratropics`` (lat >= 20),
+    ``s_extratropics`` (lat <= -20); a region with no rows on the grid is left out."""
+    lat = np.asarray(lat, dtype=np.float64)
+    w = np.cos(np.deg2rad(lat))
+    rows = {"global": np.ones(lat.shape, dtype=bool), "tropics": np.abs(lat) <= 20.0, "n_extratropics": lat >= 20.0,
+            "s_extratropics": lat <= -20.0}
+    maps = np.asarray(maps, dtype=np.float64)
+    out = {}
+    for name, sel in rows.items():
+        if sel.any():
+            ws = w[sel] / w[sel].sum()
+            out[name] = np.tensordot(maps[..., sel, :].mean(-1), ws, axes=([-1], [0]))
+    return out
+
+
 def all_metrics(pred: torch.Tensor, y: torch.Tensor, vars: Sequence[str], lat, log_postfix: str) -> Dict[str, torch.Tensor]:
     B, N, V, H, W = pred.shape
     s = ensemble_sums(pred, y, lat).double()

@@ -31,8 +31,11 @@ ensemble mean, the spread and the quantiles, default 0.1 0.5 0.9 -- the forecast
 where ``number`` stands; ``swiftk_ensemble_summary`` in fp64 on the device, one call per IC on the members the device already
 holds, so the raw trajectories never leave it on this flag's account: what a forecaster reads out of an ensemble, at
 (2 + quantiles) / members of the raw store's size; it needs an IC's members in one batch, like the metrics, but does not imply
-them and loads no verifying fields: ``--dump none --summary`` is a complete job) and ``--gpus N`` (start the N ranks from a
-bare ``python -m`` call).
+them and loads no verifying fields: ``--dump none --summary`` is a complete job), ``--maps`` (implies ``--metrics``; adds
+``evaluation_maps.zarr`` and ``evaluation_regions.json``: per lead step, variable and grid point the bias, MSE, fair CRPS and
+member variance, means over the ICs -- ``swiftk_ensemble_maps`` in fp64 on the device, accumulated per rank in one resident
+buffer -- and their latitude-weighted means over the globe, the tropics and the two extratropics: where the forecast is good,
+which no whole-grid average can tell) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
 """
 from __future__ import annotations
 
@@ -84,6 +87,9 @@ parser.add_argument("--rank-hist", action="store_true", help="implies --metrics;
                     "fields among the members per lead step and variable -> evaluation_rank_histogram.npz")
 parser.add_argument("--summary", action="store_true", help="per IC, lead step, variable and grid point the ensemble mean, spread "
                     "and quantiles -> <output name>-summary.zarr (does not imply --metrics)")
+parser.add_argument("--maps", action="store_true", help="implies --metrics; per lead step, variable and grid point the bias, MSE, "
+                    "fair CRPS and member variance, means over the ICs -> evaluation_maps.zarr, and their regional means "
+                    "(global, tropics, extratropics) -> evaluation_regions.json")
 parser.add_argument("--quantiles", type=float, nargs="+", default=[0.1, 0.5, 0.9], help="quantiles of --summary, each in [0, 1], "
                     "at most 16 (default: 0.1 0.5 0.9)")
 
@@ -159,7 +165,8 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     n_ic = len(indices)
     want_spectra = bool(getattr(args, "spectra", False))
     want_rank_hist = bool(getattr(args, "rank_hist", False))
-    want_metrics = bool(getattr(args, "metrics", False)) or want_spectra or want_rank_hist
+    want_maps = bool(getattr(args, "maps", False))
+    want_metrics = bool(getattr(args, "metrics", False)) or want_spectra or want_rank_hist or want_maps
     want_summary = bool(getattr(args, "summary", False))
     batch = int(args.batch)
     if want_metrics or want_summary:  # an IC's members must meet in one batch: whole ICs per rank and per batch
@@ -174,6 +181,7 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
     metric_sums = {}  # IC position -> [steps, nv, 4] float64 (swiftk_ensemble_sums rows)
     spectra_sum = [None]  # --spectra: [steps, nv, 3, K] float64 on the device, this rank's ICs added in IC order
     rank_hist_sum = [None]  # --rank-hist: [steps, nv, members + 1] float64 on the device, this rank's ICs added in IC order
+    maps_sum = [None]  # --maps: [steps, 4, nv, H, W] float64 resident on the device: the first IC writes it, later ICs add, in IC order
     # Output streaming (the reference copies every step to the host synchronously, generate.py:129).
     from concurrent.futures import ThreadPoolExecutor
     writer = ThreadPoolExecutor(max_workers=1)
@@ -323,7 +331,7 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
 
     def batch_metrics(units, dev_buf, truth):
         """Per IC of the batch: swiftk_ensemble_sums of its members against the verifying fields at every lead step."""
-        from .eval.metrics import ensemble_sums
+        from .eval.metrics import ensemble_maps, ensemble_sums
         lat = dataset.get_lat_lon()[0]
         uniq = sorted(set(ic for _, ic in units))
         if hasattr(truth, "result"):
@@ -340,6 +348,12 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             if want_rank_hist:
                 r = ic_rank_histogram(pred, y, lat)
                 rank_hist_sum[0] = r if rank_hist_sum[0] is None else rank_hist_sum[0] + r
+            if want_maps:  # per pixel and in IC order whatever the batch: the buffer's bits do not depend on --batch
+                first = maps_sum[0] is None
+                maps_sum[0] = ensemble_maps(pred, y, maps_sum[0])
+                if first:
+                    dist.log0(f"--maps: {maps_sum[0].numel() * 8 / 1e9:.2f} GB of fp64 maps {list(maps_sum[0].shape)} stay on each "
+                              "device until the job's end")
 
     reader = ThreadPoolExecutor(max_workers=1)
     loaders = ThreadPoolExecutor(max_workers=8)
@@ -403,6 +417,9 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             local = rank_hist_sum[0] if rank_hist_sum[0] is not None else torch.zeros(steps, nv, members + 1, dtype=torch.float64,
                                                                                       device=device)
             collect_rank_histogram(local, n_ic, members, dataset.variables, interval, norm, os.path.dirname(ofile))
+        if want_maps:
+            lat, lon = dataset.get_lat_lon()
+            collect_maps(maps_sum[0], steps, n_ic, members, dataset.variables, lat, lon, interval, os.path.dirname(ofile), device)
         return res
     return None
 
@@ -541,6 +558,67 @@ def collect_rank_histogram(local, n_ic, members, variables, interval, norm, odir
     return arrays
 
 
+MAPS_FILE, REGIONS_FILE = "evaluation_maps.zarr", "evaluation_regions.json"
+
+
+def check_maps_args(args):
+    """``--maps`` checked on the host (``ValueError``), before any rank is started or the GPU is touched."""
+    if getattr(args, "maps", False) and not 2 <= args.members <= 64:
+        raise ValueError(f"--maps takes the CRPS and the variance over 2 .. 64 members, got --members {args.members}")
+
+
+def collect_maps(local, steps, n_ic, members, variables, lat, lon, interval, odir, device="cpu"):
+    """``local`` [steps, 4, nv, H, W] fp64: this rank's sums over its ICs of the ``ensemble_maps`` terms (None for a rank without
+    ICs: it contributes zeros).  Lead step by lead step -- nothing larger than world x one [4, nv, H, W] slab is ever gathered --
+    one all-gather of the step's slabs; rank 0 adds them in rank order, divides by ``n_ic`` and writes the slab's chunks of
+    ``evaluation_maps.zarr`` (float32: ``zarrlite.create_maps_store``) and, from the fp64 means before that cast, the step's
+    entries of ``evaluation_regions.json``: region -> ``bias_`` / ``rmse_`` / ``crps_`` / ``spread_`` / ``ssr_<var>_<lead>h``, the
+    latitude-weighted regional means (``eval.metrics.region_means``) of the IC-mean maps, then rmse = sqrt(mean mse),
+    spread = sqrt(mean variance), ssr = spread / rmse."""
+    import json
+    from .eval.metrics import MAP_STATISTICS, region_means
+    from .utils import zarrlite
+    variables = [str(v) for v in variables]
+    nv, H, W = len(variables), len(lat), len(lon)
+    root = dist.get_rank() == 0
+    path, rpath = os.path.join(odir, MAPS_FILE), os.path.join(odir, REGIONS_FILE)
+    if root:
+        channels = zarrlite.create_maps_store(path, variables, lat, lon, members, steps, MAP_STATISTICS, n_ic, interval=interval)
+    regions = {}
+    for j in range(steps):
+        slab = local[j].contiguous() if local is not None else torch.zeros(4, nv, H, W, dtype=torch.float64, device=device)
+        assert tuple(slab.shape) == (4, nv, H, W) and slab.dtype == torch.float64
+        if dist.collectives_active():
+            parts = [torch.empty_like(slab) for _ in range(dist.get_world_size())]
+            tdist.all_gather(parts, slab)
+        else:
+            parts = [slab]
+        if not root:
+            continue
+        total = parts[0].cpu().numpy().copy()
+        for p in parts[1:]:
+            total += p.cpu().numpy()
+        total /= float(n_ic)
+        zarrlite.write_maps_step(path, channels, j, total.astype(np.float32))
+        for region, m in region_means(total, lat).items():   # m [4, nv]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rmse, spread = np.sqrt(m[1]), np.sqrt(m[3])
+                ssr = spread / rmse
+            out = regions.setdefault(region, {})
+            for i, v in enumerate(variables):
+                tag = f"{v}_{(j + 1) * interval}h"
+                out[f"bias_{tag}"], out[f"rmse_{tag}"], out[f"crps_{tag}"] = float(m[0, i]), float(rmse[i]), float(m[2, i])
+                out[f"spread_{tag}"], out[f"ssr_{tag}"] = float(spread[i]), float(ssr[i])
+    if not root:
+        return None
+    zarrlite.consolidate(path)
+    with open(rpath, "w") as f:
+        json.dump(regions, f, indent=1)
+    dist.log0(f"verification maps (--maps) of {n_ic} ICs x {members} members, statistics {', '.join(MAP_STATISTICS)} at {steps} "
+              f"lead steps, gathered from {dist.get_world_size()} rank(s): {path}; regional means ({', '.join(regions)}): {rpath}")
+    return regions
+
+
 def load_cfg(args) -> Cfg:
     """The run's saved composed config (generate.py:161), or the synthetic one when ``--synthetic`` names no run directory."""
     if args.synthetic and not os.path.exists(os.path.join(args.input, ".hydra", "config.yaml")):
@@ -584,6 +662,7 @@ def build_net(cfg, dataset, args, device):
 
 def main(args):
     check_summary_args(args)
+    check_maps_args(args)
     cfg = load_cfg(args)
     solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
     dist.setup_torch(backend=cfg.system.torch.backend)
@@ -598,7 +677,7 @@ def main(args):
     dist.log0("Constructing network...")
     net, ckpt_basename = build_net(cfg, dataset, args, device)
 
-    if args.spectra or args.rank_hist:
+    if args.spectra or args.rank_hist or getattr(args, "maps", False):
         args.metrics = True
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
@@ -655,5 +734,6 @@ def main(args):
 if __name__ == "__main__":
     _args = parser.parse_args()
     check_summary_args(_args)
+    check_maps_args(_args)
     dist.maybe_launch_ranks(_args.gpus, "swift_amd.generate")  # before anything touches the GPU; returns in the ranks
     main(_args)

@@ -166,6 +166,46 @@ def create_summary_store(ofile: str, variables: Sequence[str], times: np.ndarray
                                  attrs={"statistics": names, "quantiles": [float(q) for q in quantiles], "members": int(members)})
 
 
+def create_maps_store(ofile: str, variables: Sequence[str], lat: np.ndarray, lon: np.ndarray, members: int, steps: int,
+                      statistics: Sequence[str], samples: int, interval: int = 6) -> Dict[str, List[int]]:
+    """Empty store of the per-grid-point verification maps (``generate --maps``): the forecast store's variable, level, latitude
+    and longitude structure with float32 arrays of dims ``(statistic, prediction_timedelta, [level,] latitude, longitude)`` -- the
+    leads are 1 .. steps (a forecast is verified from its first step on: no lead 0) and there is no ``time`` or ``number``
+    dimension, the maps are means over the initial conditions.  One uncompressed chunk per (statistic, lead) and variable,
+    filled by ``write_maps_step``.  Group attributes: ``statistics`` (their names in order), ``members``, ``samples``.  Returns
+    {variable: channel indices}."""
+    create_group(ofile, {"statistics": [str(s) for s in statistics], "members": int(members), "samples": int(samples)})
+    td = (np.arange(1, steps + 1, dtype=np.int64) * interval * 3_600_000_000_000)
+    write_full(ofile, "prediction_timedelta", td, ["prediction_timedelta"], {"units": "nanoseconds", "dtype": "timedelta64[ns]"})
+    write_full(ofile, "latitude", np.asarray(lat, np.float32), ["latitude"])
+    write_full(ofile, "longitude", np.asarray(lon, np.float32), ["longitude"])
+    write_full(ofile, "statistic", np.arange(len(statistics), dtype=np.int64), ["statistic"])
+    comp = compress_variables(variables)
+    if any(len(lv) for lv in comp.values()):
+        write_full(ofile, "level", np.arange(max(len(lv) for lv in comp.values()), dtype=np.int64), ["level"])
+    S, n_lat, n_lon = len(statistics), len(lat), len(lon)
+    for var, levels in comp.items():
+        if levels:
+            shape, chunks = (S, steps, len(levels), n_lat, n_lon), (1, 1, len(levels), n_lat, n_lon)
+            dims = ["statistic", "prediction_timedelta", "level", "latitude", "longitude"]
+        else:
+            shape, chunks = (S, steps, n_lat, n_lon), (1, 1, n_lat, n_lon)
+            dims = ["statistic", "prediction_timedelta", "latitude", "longitude"]
+        create_array(ofile, var, shape, chunks, np.float32, dims, fill_value=0.0)
+    return variable_channels(variables)
+
+
+def write_maps_step(ofile: str, var_channels: Dict[str, List[int]], step: int, slab: np.ndarray) -> None:
+    """Lead index ``step`` (0 = the first lead) of a maps store, ``slab [S, C, H, W]``: one chunk per statistic and variable."""
+    for var, ch in var_channels.items():
+        levelled = len(_chunk_meta(ofile, var)[0]) == 5
+        for s in range(slab.shape[0]):
+            if levelled:
+                write_chunk(ofile, var, (s, step, 0, 0, 0), slab[s][None, None][:, :, ch])
+            else:
+                write_chunk(ofile, var, (s, step, 0, 0), slab[s, ch[0]][None, None])
+
+
 def write_unit(ofile: str, var_channels: Dict[str, List[int]], sample: int, member: int, traj: np.ndarray) -> None:
     """One (sample, member) trajectory ``traj [steps+1, C, H, W]`` -> one chunk per variable (chunk batch 1), generate.py:143-152."""
     for var, ch in var_channels.items():
