@@ -144,7 +144,11 @@ def zeropower_stack(G: torch.Tensor, steps: int = 5) -> torch.Tensor:
     for _ in range(steps):
         _gemm_stack(Xb, Xb, A, m, kn)                # A = X X^T
         _gemm_stack(A, A, A2, m, km)                 # A A   (A symmetric)
-        B = A2.mul_(c).add_(A.mul_(b))               # b A + c A^2 with the reference's three bf16 roundings, in place (A is rebuilt next trip)
+        # b A + c (A A), in place (A is rebuilt next trip): three bf16 roundings like the reference's b A + (c A) A, but at other
+        # places -- the reference rounds c A BEFORE the product, this rounds c (A A) after it.  Not bit-equal even where every
+        # product is exact; against the fp64 iteration the two orders err alike (bf16 noise: tests/test_muon_reference_cpu.py,
+        # slice by slice on the device in tests/test_gpu_muon.py)
+        B = A2.mul_(c).add_(A.mul_(b))
         _transpose_into(Xp.view(L * km, kn), L * km, n, XTall)  # operand forms of X for B X
         _gemm_stack(B, XT, BX, n, km)                # B X
         Xb.mul_(a).add_(BX)
