@@ -268,21 +268,36 @@ def shard_units(n_units: int, rank: int, world: int):
     return range(start, start + base + (1 if rank < rem else 0))
 
 
+def all_gather_parts(t, device=None) -> list:
+    """Every rank's ``t`` (one shape and dtype on all ranks) in rank order, or ``[t]`` when no collectives are active.  ``device``:
+    the job's device -- a host tensor of a GPU job is gathered there (RCCL moves device memory)."""
+    if not collectives_active():
+        return [t]
+    buf = t.to(device) if device is not None and torch.device(device).type == "cuda" else t
+    parts = [torch.empty_like(buf) for _ in range(get_world_size())]
+    dist.all_gather(parts, buf)
+    return parts
+
+
+def sum_in_rank_order(t) -> "np.ndarray | None":
+    """One all-gather of ``t``; rank 0 adds the ranks' parts in rank order in numpy (in ``t``'s dtype) and gets the sum, the others None."""
+    parts = all_gather_parts(t)
+    if get_rank() != 0:
+        return None
+    total = parts[0].cpu().numpy().copy()
+    for p in parts[1:]:
+        total += p.cpu().numpy()
+    return total
+
+
 def gather_rank_times(local: dict, device=None) -> dict:
     """Per-rank timing record of a measured region, for the first multi-GPU run to be read at a glance: every rank hands in
     the same keys (milliseconds or seconds as named by the caller), rank order is preserved, and every rank gets
     ``{key: [value of rank 0, value of rank 1, ...]}`` back (one all-gather of a float64 vector; a process without a group
     gets one-element lists).  bench.py / generate use it for ``compute_ms``, ``collective_ms``, ``barrier_wait_ms``."""
-    import torch
     keys = sorted(local)
-    if not collectives_active():
-        return {k: [float(local[k])] for k in keys}
-    import torch.distributed as tdist
-    world = tdist.get_world_size()
-    dev = device if device is not None else (get_torch_device() if tdist.get_backend() == "nccl" else torch.device("cpu"))
-    mine = torch.tensor([float(local[k]) for k in keys], dtype=torch.float64, device=dev)
-    out = torch.zeros(world * len(keys), dtype=torch.float64, device=dev)
-    tdist.all_gather_into_tensor(out, mine)
-    out = out.view(world, len(keys)).cpu()
-    return {k: [float(out[r, j]) for r in range(world)] for j, k in enumerate(keys)}
+    nccl = collectives_active() and dist.get_backend() == "nccl"
+    dev = device if device is not None else (get_torch_device() if nccl else torch.device("cpu"))
+    out = torch.stack(all_gather_parts(torch.tensor([float(local[k]) for k in keys], dtype=torch.float64, device=dev)), 0).cpu()
+    return {k: [float(out[r, j]) for r in range(len(out))] for j, k in enumerate(keys)}
 

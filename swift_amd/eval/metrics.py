@@ -21,12 +21,17 @@ import torch
 from .._lib import check, lib
 
 
+def lat_weights(lat) -> np.ndarray:
+    """cos(latitude), normalised to mean 1, in fp64 -- [H]: the weights of every whole-grid score here and in the sampler sweep."""
+    w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
+    return w / w.mean()
+
+
 def ensemble_sums(pred: torch.Tensor, y: torch.Tensor, lat) -> torch.Tensor:
     """pred [B, N, V, H, W], y [B, V, H, W] (device, fp32) -> [B, V, 4] weighted grid sums (see include/swiftk.h)."""
     assert pred.is_cuda and y.is_cuda and pred.ndim == 5 and y.ndim == 4
     B, N, V, H, W = pred.shape
-    w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
-    w_lat = torch.from_numpy(w / w.mean()).float().to(pred.device).contiguous()
+    w_lat = torch.from_numpy(lat_weights(lat)).float().to(pred.device).contiguous()
     pred, y = pred.contiguous().float(), y.contiguous().float()
     out = torch.zeros(B, V, 4, device=pred.device)
     check(lib().swiftk_ensemble_sums(pred.data_ptr(), y.data_ptr(), w_lat.data_ptr(), out.data_ptr(), B, N, V, H, W,
@@ -41,9 +46,8 @@ def _spectrum_tables(W: int, lat, device):
     lat = np.ascontiguousarray(lat, dtype=np.float64)
     key = (W, lat.tobytes(), str(device))
     if key not in _SPECTRUM_TABLES:
-        w = np.cos(np.deg2rad(lat))
         a = 2.0 * np.pi * np.arange(W, dtype=np.float64) / W
-        _SPECTRUM_TABLES[key] = (torch.from_numpy(w / w.mean()).to(device),
+        _SPECTRUM_TABLES[key] = (torch.from_numpy(lat_weights(lat)).to(device),
                                  torch.from_numpy(np.stack([np.cos(a), np.sin(a)], 1)).to(device).contiguous())
     return _SPECTRUM_TABLES[key]
 
@@ -180,13 +184,18 @@ def region_means(maps: np.ndarray, lat) -> Dict[str, np.ndarray]:
     return out
 
 
-def all_metrics(pred: torch.Tensor, y: torch.Tensor, vars: Sequence[str], lat, log_postfix: str) -> Dict[str, torch.Tensor]:
-    B, N, V, H, W = pred.shape
-    s = ensemble_sums(pred, y, lat).double()
-    hw = H * W
+def scores_from_sums(s: torch.Tensor, n_members: int, hw):
+    """``ensemble_sums`` rows s [B, ..., 4] (fp64) on a grid of ``hw`` points -> (rmse, crps, ssr) [...] (eval/metrics.py:39-134)."""
+    B, N = s.shape[0], n_members
     rmse = torch.sqrt(s[..., 0] / hw).mean(0)
     crps = s[..., 1].sum(0) / (B * N * hw) - (s[..., 2] / hw / (2 * N * (N - 1))).mean(0)
     ssr = torch.sqrt(s[..., 3] / hw).mean(0) / rmse
+    return rmse, crps, ssr
+
+
+def all_metrics(pred: torch.Tensor, y: torch.Tensor, vars: Sequence[str], lat, log_postfix: str) -> Dict[str, torch.Tensor]:
+    B, N, V, H, W = pred.shape
+    rmse, crps, ssr = scores_from_sums(ensemble_sums(pred, y, lat).double(), N, H * W)
     out = {}
     for i, v in enumerate(vars):
         out[f"rmse_{v}_{log_postfix}"], out[f"crps_{v}_{log_postfix}"], out[f"ssr_{v}_{log_postfix}"] = rmse[i], crps[i], ssr[i]
@@ -291,11 +300,7 @@ def evaluate_stores(truth: str, pred: str, device=None, sums_fn=None, log=print)
             sums[b] = sums_fn(np.ascontiguousarray(p.transpose(1, 0, 2, 3, 4)), np.ascontiguousarray(y), lat)
         hw = float(shape[-1] * shape[-2])
         for j, h in enumerate(leads):   # the batch statistics of eval/metrics.py:39-134 from the per-IC sums (as generate --metrics)
-            s = sums[:, j]
-            rmse = np.sqrt(s[..., 0] / hw).mean(0)
-            crps = s[..., 1].sum(0) / (B * N * hw) - (s[..., 2] / hw / (2 * N * (N - 1))).mean(0)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                ssr = np.sqrt(s[..., 3] / hw).mean(0) / rmse
+            rmse, crps, ssr = scores_from_sums(torch.from_numpy(sums[:, j]), N, hw)
             for i, nm in enumerate(names):
                 out[f"crps_{nm}_{h}h"], out[f"rmse_{nm}_{h}h"], out[f"ssr_{nm}_{h}h"] = float(crps[i]), float(rmse[i]), float(ssr[i])
         log(f"{var}: {B} initial conditions x {N} members x {T} lead times" + (f" x {L} levels" if levelled else ""))

@@ -59,6 +59,7 @@ from .. import dist, generate
 from ..config import instantiate
 from ..generating.factory import sampler_factory
 from ..rollout import unit_seed
+from . import metrics
 
 parser = argparse.ArgumentParser(parents=[generate.common_parser])
 parser.add_argument("--seed", type=int, default=0, help="Random seed")
@@ -81,9 +82,7 @@ def combos(args):
 
 def lat_weights(dataset) -> np.ndarray:
     """sampler.py:70-72 in fp64: cos(latitude), normalised to mean 1 -- [H]."""
-    lat, _ = dataset.get_lat_lon()
-    w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
-    return w / w.mean()
+    return metrics.lat_weights(dataset.get_lat_lon()[0])
 
 
 def _unit_noise(out: torch.Tensor, seeds: torch.Tensor, step: int) -> torch.Tensor:
@@ -220,15 +219,7 @@ def sample_experiment(net, dataloader, odir, args, *, score_fn: Optional[Callabl
                   f"{1e3 * el / len(mine):.1f} ms per sample, {1e3 * el / (len(mine) * evals):.2f} ms per evaluation including "
                   "staging and scoring")
 
-    if gather_fn is not None:
-        parts = gather_fn(local)
-    elif dist.collectives_active():  # as generate --metrics gathers its rows (generate.collect_metrics)
-        buf = local.to(device) if on_gpu else local
-        parts = [torch.empty_like(buf) for _ in range(world)]
-        tdist.all_gather(parts, buf)
-        parts = [q.cpu() for q in parts]
-    else:
-        parts = [local]
+    parts = gather_fn(local) if gather_fn is not None else [q.cpu() for q in dist.all_gather_parts(local, device)]
     if rank != 0:
         return None
     sse = combine_rows([q.numpy() if isinstance(q, torch.Tensor) else q for q in parts], n, world)

@@ -14,16 +14,16 @@ which caps 12 members at 6x on 8 GPUs) -- an IC's members sit next to each other
 reads each IC's state and forcing files once; rank 0 loads the checkpoint and broadcasts the
 weights over RCCL; each rank rolls its units on the device (``RolloutEngine``) and writes its
 own slices of the shared store (npy memmap, or one zarr chunk file per unit and variable:
-``utils/zarrlite.py``); a barrier closes the job.  Additive flags: ``--solver`` (``edm`` is the default of an EDMPrecond
-run), ``--num-steps``,
-``--dtype``, ``--synthetic`` (random-init weights + synthetic fields when no run directory
-exists), ``--metrics`` (ensemble RMSE / CRPS / spread-skill against the dataset's own fields,
-reduced per rank on the device and all-gathered: eval/metrics.py:39-134 without the round trip
-through the store), ``--spectra`` (implies ``--metrics``; adds ``evaluation_spectra.npz`` beside evaluation_metrics.json:
-latitude-weighted zonal power spectra of the members, of the ensemble mean and of the verifying fields per lead step and
-variable, ``swiftk_zonal_power`` in fp64 on the device -- whether the members stay as sharp as the truth, which RMSE and CRPS
-cannot tell), ``--rank-hist`` (implies ``--metrics``; adds ``evaluation_rank_histogram.npz``: per lead step and variable the
-latitude-weighted frequency with which the verifying value takes each rank 0 .. members among the members, ties spread evenly,
+``utils/zarrlite.py``); a barrier closes the job.  What else a job makes of its rollout is a list of output products, one small
+object per flag (``generating/products.py``): ``rollout_and_save`` hands each of them every IC's members once, in IC order, and
+lets it finish with its collective and its files.  Additive flags: ``--solver`` (``edm`` is the default of an EDMPrecond run),
+``--num-steps``, ``--dtype``, ``--synthetic`` (random-init weights + synthetic fields when no run directory exists), ``--metrics``
+(ensemble RMSE / CRPS / spread-skill against the dataset's own fields, reduced per rank on the device and all-gathered:
+eval/metrics.py:39-134 without the round trip through the store), ``--spectra`` (implies ``--metrics``; adds ``evaluation_spectra.npz``
+beside evaluation_metrics.json: latitude-weighted zonal power spectra of the members, of the ensemble mean and of the verifying
+fields per lead step and variable, ``swiftk_zonal_power`` in fp64 on the device -- whether the members stay as sharp as the truth,
+which RMSE and CRPS cannot tell), ``--rank-hist`` (implies ``--metrics``; adds ``evaluation_rank_histogram.npz``: per lead step and variable
+the latitude-weighted frequency with which the verifying value takes each rank 0 .. members among the members, ties spread evenly,
 ``swiftk_rank_histogram`` in exact integers and fp64 on the device -- flat is calibrated, U-shaped under-dispersive, dome-shaped
 over-dispersive, sloped biased, which one spread-skill number per variable cannot tell), ``--summary [--quantiles q ...]``
 (writes ``<output name>-summary.zarr`` beside the other outputs: per IC, lead step (lead 0 included), variable and grid point the
@@ -40,8 +40,10 @@ which no whole-grid average can tell) and ``--gpus N`` (start the N ranks from a
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import time
+from concurrent.futures import ThreadPoolExecutor
 from glob import glob
 
 import numpy as np
@@ -50,7 +52,9 @@ import torch.distributed as tdist
 
 from . import dist
 from .config import Cfg, instantiate, load_saved
+from .eval.metrics import MAP_STATISTICS, quantile_table, region_means, scores_from_sums
 from .rollout import RolloutEngine, unit_seed
+from .utils import zarrlite
 
 # the flags every CLI that loads a run shares (eval/sampler.py builds its parser on them too)
 common_parser = argparse.ArgumentParser(add_help=False)
@@ -139,131 +143,34 @@ def select_indices(n_dataset: int, samples: int, steps: int, interval: int):
 
 def create_empty_zarr(ofile, dataset, indices, members, steps, interval):
     """utils/io.py:161-235 through the stdlib writer (no zarr / xarray in this image)."""
-    from .utils import zarrlite
     lat, lon = dataset.get_lat_lon()
     times = np.array([dataset.get_time(int(i)) for i in indices], dtype="datetime64[ns]")
     zarrlite.create_forecast_store(ofile, list(dataset.variables), times, lat, lon, members, steps, interval=interval, batch=1)
 
 
-def unit_of(u: int, members: int):
-    """Flattened unit id -> (member, position of its IC in ``indices``); IC-major, so an IC's members are adjacent."""
-    return u % members, u // members
-
-
-def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, steps: int, ofile: str, device, args):
-    """generate.py:48-154 with (member, IC) units instead of members as the sharded work item."""
-    dump = getattr(args, "dump", "numpy") or "zarr"
-    if dump == "numpy":
-        store = np.lib.format.open_memmap(ofile, mode="r+")  # shape / data offset of the .npy the launcher created
-        store_fd = os.open(ofile, os.O_WRONLY)
-        store_off, store_shape = int(store.offset), tuple(store.shape)   # [samples, members, steps + 1, nv, H, W] float32
-        del store
-    elif dump == "zarr":
-        from .utils import zarrlite
-        var_channels = zarrlite.variable_channels(list(dataset.variables))
-    rank, world = dist.get_rank(), dist.get_world_size()
-    n_ic = len(indices)
-    want_spectra = bool(getattr(args, "spectra", False))
-    want_rank_hist = bool(getattr(args, "rank_hist", False))
-    want_maps = bool(getattr(args, "maps", False))
-    want_metrics = bool(getattr(args, "metrics", False)) or want_spectra or want_rank_hist or want_maps
-    want_summary = bool(getattr(args, "summary", False))
-    batch = int(args.batch)
-    if want_metrics or want_summary:  # an IC's members must meet in one batch: whole ICs per rank and per batch
-        batch = max(members, batch // members * members)
-        ic_range = dist.shard_units(n_ic, rank, world)
-        mine = range(ic_range.start * members, ic_range.stop * members)
-    else:
-        mine = dist.shard_units(members * n_ic, rank, world)  # unit u = ic * members + member
-    nv = len(dataset.variables)
-    interval = engine.interval
-    done = 0
-    metric_sums = {}  # IC position -> [steps, nv, 4] float64 (swiftk_ensemble_sums rows)
-    spectra_sum = [None]  # --spectra: [steps, nv, 3, K] float64 on the device, this rank's ICs added in IC order
-    rank_hist_sum = [None]  # --rank-hist: [steps, nv, members + 1] float64 on the device, this rank's ICs added in IC order
-    maps_sum = [None]  # --maps: [steps, 4, nv, H, W] float64 resident on the device: the first IC writes it, later ICs add, in IC order
-    # Output streaming (the reference copies every step to the host synchronously, generate.py:129).
-    from concurrent.futures import ThreadPoolExecutor
-    writer = ThreadPoolExecutor(max_workers=1)
+def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, steps: int, ofile: str, device, args, products=None):
+    """generate.py:48-154 with (member, IC) units instead of members as the sharded work item.  Batch by batch: inputs staged one
+    batch ahead, the rollout, every product (``generating/products.py``; default: those of ``args``) fed each IC of the batch once
+    in ascending IC order -- so that no product's sums depend on ``--batch`` -- and the trajectory handed to the raw store's writer;
+    then every product finishes (its collective; on rank 0 its files).  Returns rank 0's metrics dict (``--metrics``), else None."""
+    from .generating.products import StoreWriter, plan_units, products_from_args
+    nv, interval, n_ic = len(dataset.variables), engine.interval, len(indices)
     on_gpu = torch.device(device).type == "cuda"   # (the host-logic tests drive this loop with a CPU stand-in engine)
-    copy_stream = torch.cuda.Stream(device=device) if on_gpu else None
-    pending = None  # CPU stand-in path only: the writer's future for the previous batch
-    # GPU path: the output leaves STEP BY STEP -- as soon as a lead step of the batch is enqueued its [B, nv, H, W] slab is copied
-    # on the side stream into one of RING pinned slabs (RING x 0.87 GB at 96 units, instead of two whole pinned trajectories:
-    # 2 x 52 GB for 60 steps) and written from there while the following steps compute; at the end of a batch only its last
-    # slabs are still on their way, so a job of ONE batch (12 members x 8 ICs on a GPU) overlaps its output as well
-    RING = 4
-    ring, ring_busy, ring_pos = [None], [None] * RING, [0]
-
-    t_host = [0.0, 0.0]  # seconds in input staging / output writes (host side)
-
-    def flush(p):
-        """CPU stand-in path: one batch's whole trajectory [steps+1, B, ...] (the GPU path writes step by step, flush_step)."""
-        host, us = p
-        t1 = time.time()
-        h = host.numpy()
-        if dump == "numpy":
-            # buffer is step-major [steps+1, B, ...]: every (step, unit) slab is contiguous on both sides, so the store is filled
-            # by positional writes from the loader threads (pwrite releases the GIL; assigning into a memory map of the file
-            # page-faults its way through fresh pages at ~3 GB/s however many threads share the mapping -- less than one GPU
-            # produces: 330 sample-steps/s x 9 MB)
-            slab = int(np.prod(store_shape[3:])) * 4
-            per_unit = store_shape[2] * slab
-
-            def put(kmi):
-                k, (m, ic) = kmi
-                base = store_off + (ic * store_shape[1] + m) * per_unit
-                for i in range(h.shape[0]):
-                    os.pwrite(store_fd, memoryview(h[i, k]).cast("B"), base + i * slab)
-
-            list(loaders.map(put, enumerate(us)))
-        else:  # one chunk file per unit and variable: independent files, written by a few threads
-            list(loaders.map(lambda kmi: zarrlite.write_unit(ofile, var_channels, kmi[1][1], kmi[1][0], h[:, kmi[0]]),
-                             enumerate(us)))
-        t_host[1] += time.time() - t1
-
-    def flush_step(ev, host, us, j):
-        ev.synchronize()
-        t1 = time.time()
-        h = host.numpy()  # [B, nv, H, W] of lead step j
-        if dump == "numpy":
-            slab = int(np.prod(store_shape[3:])) * 4
-            per_unit = store_shape[2] * slab
-            list(loaders.map(lambda kmi: os.pwrite(store_fd, memoryview(h[kmi[0]]).cast("B"),
-                                                   store_off + (kmi[1][1] * store_shape[1] + kmi[1][0]) * per_unit + j * slab),
-                             enumerate(us)))
-        else:
-            list(loaders.map(lambda kmi: zarrlite.write_unit_step(ofile, var_channels, kmi[1][1], kmi[1][0], j, h[kmi[0]]),
-                             enumerate(us)))
-        t_host[1] += time.time() - t1
-
-    def stream_out(us):
-        """after_step hook of RolloutEngine.run for one batch."""
-        def hook(j, slab_dev):
-            B_ = slab_dev.shape[0]
-            if ring[0] is None or ring[0].shape[1] < B_:
-                for f in ring_busy:
-                    if f is not None:
-                        f.result()
-                ring[0] = torch.empty(RING, B_, *slab_dev.shape[1:], dtype=torch.float32, pin_memory=True)
-            slot = ring_pos[0] % RING
-            ring_pos[0] += 1
-            if ring_busy[slot] is not None:
-                ring_busy[slot].result()  # the writer is done with this slab (back-pressure when the store is slower than the GPU)
-            host = ring[0][slot, :B_]
-            ready, ev = torch.cuda.Event(), torch.cuda.Event()
-            ready.record()
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(ready)
-                host.copy_(slab_dev, non_blocking=True)
-                ev.record(copy_stream)
-            ring_busy[slot] = writer.submit(flush_step, ev, host, us, j)
-        return hook
+    reader = ThreadPoolExecutor(max_workers=1)
+    loaders = ThreadPoolExecutor(max_workers=8)
+    stagers = ThreadPoolExecutor(max_workers=4)  # forcing slabs, step by step (their own pool: output writes must not queue behind them)
+    products = products_from_args(args, dataset, members, steps, ofile, device, n_ic, interval, loaders) if products is None else products
+    need_truth = any(p.needs_truth for p in products)
+    batch, mine = plan_units(products, n_ic, members, int(args.batch), dist.get_rank(), dist.get_world_size())
+    store = StoreWriter(getattr(args, "dump", "numpy") or "zarr", ofile, dataset, loaders, device)
+    t_stage = 0.0  # seconds in input staging (host side)
 
     def stage(s):
         """Host-side inputs of the batch starting at unit s (pinned tensors; runs on the reader thread, one batch ahead)."""
+        nonlocal t_stage
         t1 = time.time()
-        units = [unit_of(u, members) for u in range(s, min(s + batch, mine.stop))]
+        # flattened unit id -> (member, position of its IC in ``indices``); IC-major, so an IC's members are adjacent
+        units = [(u % members, u // members) for u in range(s, min(s + batch, mine.stop))]
         ics = [indices[ic] for _, ic in units]
         state = getattr(dataset, "get_state", None)  # one read per IC; dataset[j] would also read j's training target
         x0 = {int(j): (dataset.standardize_x(state(int(j))) if state else dataset[int(j)][0][0][:nv]) for j in set(ics)}
@@ -272,7 +179,7 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
         # after all `steps` of them); the CPU stand-in of the host-logic tests takes the whole tensor
         forc = engine.stage_forcings_lazily(ics, steps, device, stagers) if on_gpu else engine.stage_forcings(ics, steps, "cpu")
         truth = None
-        if want_metrics:  # verifying fields of every lead step, physical units, one copy per IC of the batch
+        if need_truth:  # verifying fields of every lead step, physical units, one copy per IC of the batch
             uniq = sorted(set(ic for _, ic in units))
             get = state if state else (lambda j: dataset.unstandardize_x(dataset[j][0][0][:nv]))
             jobs = [int(indices[ic]) + (i + 1) * interval // 6 for ic in uniq for i in range(steps)]
@@ -286,80 +193,12 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
             truth = stagers.submit(load_truth) if on_gpu else load_truth()
         if on_gpu:
             X0 = X0.pin_memory()
-        t_host[0] += time.time() - t1
+        t_stage += time.time() - t1
         return units, X0, forc, truth
 
-    # --summary: the [steps + 1, 2 + Q, nv, H, W] result of an IC stays on the device until the summary thread has taken it --
-    # through one pinned buffer on a stream of its own -- and written its 2 + Q chunk files per variable; the rollout loop never
-    # waits for a copy, only, one batch's worth of ICs later, for the files (back-pressure when the store is slower than the GPU)
-    summary_file = summary_path(ofile)
-    summary_writer = ThreadPoolExecutor(max_workers=1) if want_summary else None
-    summary_stream = torch.cuda.Stream(device=device) if want_summary and on_gpu else None
-    summary_host, summary_pending = [None], []
-
-    def flush_summary(out_dev, ready, ic):
-        with torch.cuda.device(device):
-            if summary_host[0] is None:
-                summary_host[0] = torch.empty(out_dev.shape, dtype=torch.float32, pin_memory=True)
-            with torch.cuda.stream(summary_stream):
-                summary_stream.wait_event(ready)
-                summary_host[0].copy_(out_dev, non_blocking=True)
-            summary_stream.synchronize()
-        del out_dev
-        t1 = time.time()
-        h = summary_host[0].numpy()  # [steps + 1, 2 + Q, nv, H, W]
-        list(loaders.map(lambda k: zarrlite.write_unit(summary_file, summary_channels, ic, k, h[:, k]), range(h.shape[1])))
-        t_host[1] += time.time() - t1
-
-    def batch_summary(units, dev_buf):
-        """Per IC of the batch: swiftk_ensemble_summary of its members at every lead step, lead 0 included."""
-        from .eval.metrics import ensemble_summary
-        uniq = sorted(set(ic for _, ic in units))
-        for ic in uniq:
-            slots = [b for b, (_, i) in enumerate(units) if i == ic]
-            assert len(slots) == members and slots == list(range(slots[0], slots[0] + members))
-            out = ensemble_summary(dev_buf[:, slots[0]:slots[0] + members], args.quantiles)
-            ready = torch.cuda.Event()
-            ready.record()
-            while len(summary_pending) >= len(uniq):
-                summary_pending.pop(0).result()
-            summary_pending.append(summary_writer.submit(flush_summary, out, ready, ic))
-
-    if want_summary:
-        from .utils import zarrlite
-        summary_channels = zarrlite.variable_channels(list(dataset.variables))
-
-    def batch_metrics(units, dev_buf, truth):
-        """Per IC of the batch: swiftk_ensemble_sums of its members against the verifying fields at every lead step."""
-        from .eval.metrics import ensemble_maps, ensemble_sums
-        lat = dataset.get_lat_lon()[0]
-        uniq = sorted(set(ic for _, ic in units))
-        if hasattr(truth, "result"):
-            truth = truth.result()
-        for k, ic in enumerate(uniq):
-            slots = [b for b, (_, i) in enumerate(units) if i == ic]
-            assert len(slots) == members and slots == list(range(slots[0], slots[0] + members))
-            pred = dev_buf[1:, slots[0]:slots[0] + members].contiguous()       # [steps, members, nv, H, W]
-            y = truth[k].to(pred.device, non_blocking=True)
-            metric_sums[ic] = ensemble_sums(pred, y, lat).double().cpu()
-            if want_spectra:
-                s = ic_spectra(pred, y, lat)
-                spectra_sum[0] = s if spectra_sum[0] is None else spectra_sum[0] + s
-            if want_rank_hist:
-                r = ic_rank_histogram(pred, y, lat)
-                rank_hist_sum[0] = r if rank_hist_sum[0] is None else rank_hist_sum[0] + r
-            if want_maps:  # per pixel and in IC order whatever the batch: the buffer's bits do not depend on --batch
-                first = maps_sum[0] is None
-                maps_sum[0] = ensemble_maps(pred, y, maps_sum[0])
-                if first:
-                    dist.log0(f"--maps: {maps_sum[0].numel() * 8 / 1e9:.2f} GB of fp64 maps {list(maps_sum[0].shape)} stay on each "
-                              "device until the job's end")
-
-    reader = ThreadPoolExecutor(max_workers=1)
-    loaders = ThreadPoolExecutor(max_workers=8)
-    stagers = ThreadPoolExecutor(max_workers=4)  # forcing slabs, step by step (their own pool: output writes must not queue behind them)
     starts = list(range(mine.start, mine.stop, batch))
     nxt = reader.submit(stage, starts[0]) if starts else None
+    done = 0
     for bi, s in enumerate(starts):
         units, X0, forc, truth = nxt.result()
         nxt = reader.submit(stage, starts[bi + 1]) if bi + 1 < len(starts) else None
@@ -367,61 +206,35 @@ def rollout_and_save(engine: RolloutEngine, dataset, indices, members: int, step
         if not on_gpu:
             forc = forc.to(device, non_blocking=True)
         traj = engine.run(X0, forc, steps, seeds=[unit_seed(m, indices[ic]) for m, ic in units],  # [B, steps+1, ...] view
-                          **({"after_step": stream_out(units)} if on_gpu and dump != "none" else {}))
+                          **({"after_step": store.after_step(units)} if on_gpu else {}))
         dev_buf = traj.transpose(0, 1)      # the contiguous step-major buffer behind it
-        if want_metrics:
-            batch_metrics(units, dev_buf, truth)
-        if want_summary:
-            batch_summary(units, dev_buf)
+        truth = truth.result() if hasattr(truth, "result") else truth
+        # every IC's truth products before any IC's other products, the order of device calls this loop has always had: the summary
+        # kernel of one IC never sits in front of the next IC's metric sums, whose copy to the host the loop waits for
+        for with_truth in (True, False):
+            feed = [p for p in products if p.needs_truth == with_truth]
+            for k, ic in enumerate(sorted(set(ic for _, ic in units)) if feed else []):
+                slots = [b for b, (_, i) in enumerate(units) if i == ic]
+                assert len(slots) == members and slots == list(range(slots[0], slots[0] + members))
+                ic_traj = dev_buf[:, slots[0]:slots[0] + members]                    # [steps + 1, members, nv, H, W]
+                pred = ic_traj[1:].contiguous() if with_truth else None             # the one copy every truth product shares
+                y = truth[k].to(pred.device, non_blocking=True) if with_truth else None
+                for p in feed:
+                    p.add_ic(ic, ic_traj, pred, y)
         if on_gpu:
-            dev_buf.record_stream(copy_stream)  # its last slabs may still be on their way to the host
-            done += len(units)
-            dist.log0(f"rank 0: {done}/{len(mine)} units")
-            continue
-        if dump == "none":  # metrics only: nothing leaves the device but the reduced sums
-            done += len(units)
-            dist.log0(f"rank 0: {done}/{len(mine)} units")
-            continue
-        # CPU stand-in engine (host-logic tests): the whole step-major trajectory goes to the writer thread at once
-        host = dev_buf.contiguous()
-        if pending is not None:
-            pending.result()                # one trajectory in flight on the writer thread
-        pending = writer.submit(flush, (host, units))  # host-side write under the next batch's staging
+            dev_buf.record_stream(store.copy_stream)  # its last slabs may still be on their way to the host
+        else:
+            store.submit_traj(units, dev_buf)
         done += len(units)
         dist.log0(f"rank 0: {done}/{len(mine)} units")
-    if pending is not None:
-        pending.result()
-    for f in ring_busy:
-        if f is not None:
-            f.result()
-    for f in summary_pending:
-        f.result()
-    if summary_writer is not None:
-        summary_writer.shutdown()
-    writer.shutdown()
+    store.close()
     reader.shutdown()
-    loaders.shutdown()
     stagers.shutdown()
-    if dump == "numpy":
-        os.close(store_fd)
-    dist.log0(f"host side: {t_host[0]:.2f} s staging inputs, {t_host[1]:.2f} s writing outputs")
-    if want_metrics:
-        res = collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, device, os.path.dirname(ofile))
-        if want_spectra:
-            K = dataset.img_resolution[1] // 2 + 1
-            local = spectra_sum[0] if spectra_sum[0] is not None else torch.zeros(steps, nv, 3, K, dtype=torch.float64, device=device)
-            collect_spectra(local, n_ic, members, dataset.variables, interval, os.path.dirname(ofile))
-        if want_rank_hist:
-            w = np.cos(np.deg2rad(np.asarray(dataset.get_lat_lon()[0], dtype=np.float64)))
-            norm = float(dataset.img_resolution[1]) * float((w / w.mean()).sum())   # what one plane's bins sum to: W sum(w_lat)
-            local = rank_hist_sum[0] if rank_hist_sum[0] is not None else torch.zeros(steps, nv, members + 1, dtype=torch.float64,
-                                                                                      device=device)
-            collect_rank_histogram(local, n_ic, members, dataset.variables, interval, norm, os.path.dirname(ofile))
-        if want_maps:
-            lat, lon = dataset.get_lat_lon()
-            collect_maps(maps_sum[0], steps, n_ic, members, dataset.variables, lat, lon, interval, os.path.dirname(ofile), device)
-        return res
-    return None
+    results = [p.finish() for p in products]   # (the summary's last files are still being written by the loaders)
+    loaders.shutdown()
+    dist.log0(f"host side: {t_stage:.2f} s staging inputs, "
+              f"{store.seconds + sum(getattr(p, 'seconds', 0.0) for p in products):.2f} s writing outputs")
+    return next((r for r in results if r is not None), None)  # (only the metric sums return something: rank 0's dict)
 
 
 def summary_path(ofile: str) -> str:
@@ -430,7 +243,6 @@ def summary_path(ofile: str) -> str:
 
 
 def create_empty_summary(sfile, dataset, indices, members, steps, interval, quantiles):
-    from .utils import zarrlite
     lat, lon = dataset.get_lat_lon()
     times = np.array([dataset.get_time(int(i)) for i in indices], dtype="datetime64[ns]")
     zarrlite.create_summary_store(sfile, list(dataset.variables), times, lat, lon, members, steps, quantiles, interval=interval)
@@ -439,7 +251,6 @@ def create_empty_summary(sfile, dataset, indices, members, steps, interval, quan
 def check_summary_args(args):
     """``--summary`` / ``--quantiles`` checked on the host (``ValueError``), before any rank is started or the GPU is touched."""
     if getattr(args, "summary", False):
-        from .eval.metrics import quantile_table
         if not 2 <= args.members <= 64:
             raise ValueError(f"--summary takes the statistics over 2 .. 64 members, got --members {args.members}")
         quantile_table(args.quantiles, args.members)
@@ -448,28 +259,16 @@ def check_summary_args(args):
 def collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, device, odir):
     """Output collection over RCCL: every rank contributes the ensemble sums of its ICs ([n_ic, steps, nv, 4], zeros
     elsewhere), one all-gather, rank 0 turns them into the reference's metric names (eval/metrics.py:39-134)."""
-    import json
     local = torch.zeros(n_ic, steps, nv, 4, dtype=torch.float64)
     for ic, v in metric_sums.items():
         local[ic] = v
-    if dist.collectives_active():
-        on_gpu = torch.device(device).type == "cuda"
-        buf = local.to(device) if on_gpu else local
-        parts = [torch.empty_like(buf) for _ in range(dist.get_world_size())]
-        tdist.all_gather(parts, buf)
-        total = torch.stack(parts, 0).sum(0).cpu()
-    else:
-        total = local
+    total = torch.stack(dist.all_gather_parts(local, device), 0).sum(0).cpu() if dist.collectives_active() else local
     if dist.get_rank() != 0:
         return None
     H, W = dataset.img_resolution
-    hw, N = H * W, members
     res = {}
     for j in range(steps):
-        s = total[:, j]                                                   # [n_ic, nv, 4]
-        rmse = torch.sqrt(s[..., 0] / hw).mean(0)
-        crps = s[..., 1].sum(0) / (n_ic * N * hw) - (s[..., 2] / hw / (2 * N * (N - 1))).mean(0)
-        ssr = torch.sqrt(s[..., 3] / hw).mean(0) / rmse
+        rmse, crps, ssr = scores_from_sums(total[:, j], members, H * W)    # [n_ic, nv, 4] -> [nv] each
         for i, v in enumerate(dataset.variables):
             tag = f"{(j + 1) * interval}h"
             res[f"rmse_{v}_{tag}"], res[f"crps_{v}_{tag}"], res[f"ssr_{v}_{tag}"] = float(rmse[i]), float(crps[i]), float(ssr[i])
@@ -480,34 +279,17 @@ def collect_metrics(metric_sums, n_ic, steps, nv, members, dataset, interval, de
     return res
 
 
-def ic_spectra(pred, y, lat):
-    """One IC's zonal power spectra: pred [steps, members, nv, H, W] and truth y [steps, nv, H, W] (device, fp32) ->
-    [steps, nv, 3, K] fp64 on the device: the member spectra summed over the members, the spectrum of the ensemble mean, the
-    spectrum of the verifying fields."""
-    from .eval.metrics import zonal_power
-    steps, members, nv, H, W = pred.shape
-    member = zonal_power(pred.view(steps * members, nv, H, W), lat).view(steps, members, nv, -1).sum(1)
-    return torch.stack([member, zonal_power(pred, lat, group=members), zonal_power(y.contiguous(), lat)], 2)
-
-
 SPECTRA_FILE = "evaluation_spectra.npz"
 
 
 def collect_spectra(local, n_ic, members, variables, interval, odir):
-    """``local`` [steps, nv, 3, K] fp64: this rank's sums over its ICs (``ic_spectra`` rows).  One all-gather of these arrays (not
+    """``local`` [steps, nv, 3, K] fp64: this rank's sums over its ICs (the ``Spectra`` product's).  One all-gather of these arrays (not
     of per-IC rows: 64 ICs x 60 steps of them are 0.8 GB per rank), rank 0 adds them in rank order, divides by the number of
     terms and writes ``evaluation_spectra.npz`` (plain arrays, no pickles): wavenumber [K], lead_hours [steps], variables [nv],
     member / ensemble_mean / truth [steps, nv, K] (means over ICs and members / ICs / ICs), members, samples."""
-    if dist.collectives_active():
-        parts = [torch.empty_like(local) for _ in range(dist.get_world_size())]
-        tdist.all_gather(parts, local)
-    else:
-        parts = [local]
-    if dist.get_rank() != 0:
+    total = dist.sum_in_rank_order(local)
+    if total is None:
         return None
-    total = parts[0].cpu().numpy().copy()
-    for p in parts[1:]:
-        total += p.cpu().numpy()
     steps, nv, _, K = total.shape
     arrays = dict(wavenumber=np.arange(K, dtype=np.int64), lead_hours=(np.arange(steps, dtype=np.int64) + 1) * int(interval),
                   variables=np.array([str(v) for v in variables], dtype=np.str_),
@@ -520,32 +302,18 @@ def collect_spectra(local, n_ic, members, variables, interval, odir):
     return arrays
 
 
-def ic_rank_histogram(pred, y, lat):
-    """One IC's rank histograms: pred [steps, members, nv, H, W] and truth y [steps, nv, H, W] (device, fp32) ->
-    [steps, nv, members + 1] fp64 on the device, each row summing to W sum(w_lat)."""
-    from .eval.metrics import rank_histogram
-    return rank_histogram(pred, y.contiguous(), lat)
-
-
 RANK_HIST_FILE = "evaluation_rank_histogram.npz"
 
 
 def collect_rank_histogram(local, n_ic, members, variables, interval, norm, odir):
-    """``local`` [steps, nv, members + 1] fp64: this rank's sums over its ICs (``ic_rank_histogram`` rows).  One all-gather of
+    """``local`` [steps, nv, members + 1] fp64: this rank's sums over its ICs (the ``RankHistogram`` product's).  One all-gather of
     these arrays (never of per-IC rows), rank 0 adds them in rank order, divides by ``n_ic * norm`` (``norm`` = W sum(w_lat), what
     one plane's bins sum to) so that each (lead, variable) row sums to 1, and writes ``evaluation_rank_histogram.npz`` (plain
     arrays, no pickles): rank [members + 1], lead_hours [steps], variables [nv], frequency [steps, nv, members + 1], members,
     samples."""
-    if dist.collectives_active():
-        parts = [torch.empty_like(local) for _ in range(dist.get_world_size())]
-        tdist.all_gather(parts, local)
-    else:
-        parts = [local]
-    if dist.get_rank() != 0:
+    total = dist.sum_in_rank_order(local)
+    if total is None:
         return None
-    total = parts[0].cpu().numpy().copy()
-    for p in parts[1:]:
-        total += p.cpu().numpy()
     steps, nv, bins = total.shape
     assert bins == members + 1
     arrays = dict(rank=np.arange(bins, dtype=np.int64), lead_hours=(np.arange(steps, dtype=np.int64) + 1) * int(interval),
@@ -575,9 +343,6 @@ def collect_maps(local, steps, n_ic, members, variables, lat, lon, interval, odi
     entries of ``evaluation_regions.json``: region -> ``bias_`` / ``rmse_`` / ``crps_`` / ``spread_`` / ``ssr_<var>_<lead>h``, the
     latitude-weighted regional means (``eval.metrics.region_means``) of the IC-mean maps, then rmse = sqrt(mean mse),
     spread = sqrt(mean variance), ssr = spread / rmse."""
-    import json
-    from .eval.metrics import MAP_STATISTICS, region_means
-    from .utils import zarrlite
     variables = [str(v) for v in variables]
     nv, H, W = len(variables), len(lat), len(lon)
     root = dist.get_rank() == 0
@@ -588,16 +353,9 @@ def collect_maps(local, steps, n_ic, members, variables, lat, lon, interval, odi
     for j in range(steps):
         slab = local[j].contiguous() if local is not None else torch.zeros(4, nv, H, W, dtype=torch.float64, device=device)
         assert tuple(slab.shape) == (4, nv, H, W) and slab.dtype == torch.float64
-        if dist.collectives_active():
-            parts = [torch.empty_like(slab) for _ in range(dist.get_world_size())]
-            tdist.all_gather(parts, slab)
-        else:
-            parts = [slab]
+        total = dist.sum_in_rank_order(slab)
         if not root:
             continue
-        total = parts[0].cpu().numpy().copy()
-        for p in parts[1:]:
-            total += p.cpu().numpy()
         total /= float(n_ic)
         zarrlite.write_maps_step(path, channels, j, total.astype(np.float32))
         for region, m in region_means(total, lat).items():   # m [4, nv]
@@ -677,8 +435,8 @@ def main(args):
     dist.log0("Constructing network...")
     net, ckpt_basename = build_net(cfg, dataset, args, device)
 
-    if args.spectra or args.rank_hist or getattr(args, "maps", False):
-        args.metrics = True
+    from .generating.products import MetricSums, product_types
+    args.metrics = MetricSums in product_types(args)  # (--spectra, --rank-hist and --maps imply the metric sums)
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
         if args.dump == "none":
@@ -717,10 +475,8 @@ def main(args):
     dist.log0(f"Done! Took {el:.3f} seconds: {n} sample-steps, {n / el:.1f} sample-steps/s including forcing staging and output "
               f"streaming to {os.path.basename(ofile)}.")
     if args.dump == "zarr" and dist.get_rank() == 0:  # generate.py:281-285
-        from .utils import zarrlite
         zarrlite.consolidate(ofile)
     if args.summary and dist.get_rank() == 0:  # (after the barrier: every rank's chunk files are in place)
-        from .utils import zarrlite
         zarrlite.consolidate(summary_path(ofile))
         dist.log0(f"ensemble summary (--summary) of {len(indices)} ICs x {args.members} members, statistics "
                   f"{', '.join(zarrlite.statistic_names(args.quantiles))} at {args.steps + 1} lead steps: {summary_path(ofile)}")
