@@ -367,6 +367,11 @@ int swiftk_profile_gemm(int epilogue, int64_t N);
  *          value (tools/gemm_epilogue_probe.py times the four),
  * key 32 = diagnostic of key 31, for tests: bit n is set once swiftk_gemm has launched the SL = n instantiation of the 352-wide ping-pong
  *          kernel (n = the bits of key 31 that applied; n = 0 the old forms); setting the key to any value clears the mask,
+ * key 33 = swiftk_swinv2_forward (bf16 engine, 8-bit pair stream, d = 1056 / 1280): the ModulatedNorm behind the plain wo / w2 writes the
+ *          new hi to a second buffer and the two buffers change roles (1, default: swiftk_modnorm_residual_pair_to; 0 = in place:
+ *          swiftk_modnorm_residual_pair).  Bit-equal results,
+ * key 34 = diagnostic of key 33, for tests: the number of times the last swiftk_swinv2_forward exchanged the two buffers (2 x depth on the
+ *          plain path, 0 elsewhere); setting the key clears it,
  * key 25 = clears through hipMemsetAsync instead of a kernel (0; diagnosis only; bit 1 = the library's internal clears --
  * swiftk_modnorm_bwd's workspace, swiftk_scm_target's scratch --, bit 2 = swiftk_zero_f32, bit 4 = a check kernel behind
  * swiftk_modnorm_bwd's clear records what it left non-zero: swiftk_zero_check_report). */

@@ -184,6 +184,8 @@ extern int g_x3_qkonly;  // tuning key 27
 extern int g_x3_attnpv;  // tuning key 28
 extern int g_fwd_tail;   // tuning key 29 (forward.hip)
 extern int g_fwd_pepair;  // tuning key 19
+extern int g_fwd_pingpong;  // tuning key 33 (forward.hip)
+extern int g_fwd_pingpong_seen;  // tuning key 34
 extern int g_modnorm_nt;  // tuning key 6
 extern int g_persist_wgs;  // tuning key 2: workgroups of the persistent matrix kernels (GEMM, fused to_qkv + attention)
 extern int g_fwd_rownorm;  // tuning key 23: wo / w2 + norm as one complete-row kernel up to this many units per step

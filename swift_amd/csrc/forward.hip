@@ -14,6 +14,8 @@ int g_fwd_splitk = 2;  // tuning key 14: 2 = bf16 slabs, 1 = fp32 slabs
 int g_fwd_tail = 3;    // tuning key 29: bit 0 = wo / w2 with the walk's last round as two k-halves where that round is at most half full
                        // (3, 4, 6, 11, 12 .. units per step at dim 1056), bit 1 = the packed two-slab norm behind the one-unit split-K
 int g_fwd_pepair = 1;  // tuning key 19: the patch embedding's epilogue writes the pair form itself
+int g_fwd_pingpong = 1;  // tuning key 33: the plain wo / w2 norm writes the new hi to a second buffer (the two alternate) instead of in place
+int g_fwd_pingpong_seen = 0;  // tuning key 34 (diagnostic): exchanges of the two buffers in the last swiftk_swinv2_forward
 int g_x3_attnpv = 1;  // tuning key 28: split engine, P V of the fp32 attention kernel as three bf16 products
 int g_x3_qkonly = 2;  // tuning key 27: split engine's exact to_qkv recompute: 2 = each hot head alone (q, k, v), 1 = hot pairs' q and k, 0 = hot pairs
 int g_x3_ffsplit = 1;  // tuning key 18: split engine, w1 writes w2's operand blocks itself  // tuning key 14: wo / w2 as two k-ranges into fp32 slabs when their tiles fill less than half the chip (one unit per step)
@@ -31,7 +33,7 @@ __global__ __launch_bounds__(256) void zero_cols_kernel(char* p, int64_t ld_b, i
 }
 
 struct Layout {
-    int64_t emb, h1, lat, mod, ape, x, xt, xlo, qkv, att, y, yslab, hmid, tok, kscr, a3, a3h, total;
+    int64_t emb, h1, lat, mod, ape, x, xt, xt2, xlo, qkv, att, y, yslab, hmid, tok, kscr, a3, a3h, total;
 };
 
 inline int64_t al(int64_t v) { return (v + 255) & ~(int64_t)255; }
@@ -95,6 +97,9 @@ Layout make_layout(const swiftk_model* m, int B) {
     L.ape = o; o += al(M * m->kpe * es);
     L.x = o; o += al(M * d * 4);
     L.xt = o; o += al(M * m->kd * es);
+    // second hi buffer of the pair-form stream (tuning key 33; sized whatever the key says now, since it may change after the
+    // workspace was sized): the widths swiftk_modnorm_residual_pair_to takes
+    L.xt2 = o; o += m->dtype == SWIFTK_BF16 && (d == 1056 || d == 1280) && M % 16 == 0 ? al(M * m->kd * es) : 0;
     L.xlo = o; o += m->dtype == SWIFTK_BF16 ? al(M * d * 2) : 0;  // low half of the pair-form residual stream
     L.qkv = o; o += al(M * 3 * inner * es);
     L.att = o; o += al(M * att_ld(m) * es);
@@ -280,6 +285,30 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
         rn_rows = (M / 32 <= g_persist_wgs) ? 32 : 64;
         if (ntok % rn_rows) rn_rows = 0;
     }
+    // The plain wo / w2 + norm path: the norm reads hi from one buffer and writes the new hi to the other, and the two change roles
+    // (xT always names the current one; 2 x depth exchanges leave it where it started).  The same kernel and the same values as in
+    // place -- but the pass moves its bytes faster when it does not write the hi lines it has just read: 1.29 against 1.38 ms per
+    // launch at 96 units; the one-byte low part stays in place, moving it as well changes nothing (profiles/r10a_modnorm_rowstats.txt).
+    // The small-batch forms above keep their in-place kernels.
+    void* xT2 = ws + L.xt2;
+    g_fwd_pingpong_seen = 0;
+    const bool pingpong = pair && lo_bits == 8 && (g_fwd_pingpong & 1) && (d == 1056 || d == 1280) && M % 16 == 0;
+    if (pingpong && m->kd > d) {  // (the second buffer is a GEMM operand too: finite k-padding)
+        hipLaunchKernelGGL(zero_cols_kernel, dim3(1024), dim3(256), 0, st, static_cast<char*>(xT2), m->kd * 2, (int64_t)d * 2,
+                           (m->kd - d) * 2, M);
+        SWIFTK_CHECK_LAUNCH();
+    }
+    auto PAIRNORM = [&](const float* g_, const float* b_, const float* mod_) -> int {
+        if (pingpong) {
+            const int rc = swiftk_modnorm_residual_pair_to(y, d, xT, xT2, m->kd, xlo, d, lo_bits, g_, b_, mod_, ldmod, M, d, ntok, 1e-6f, stream);
+            if (rc == 0) {
+                std::swap(xT, xT2);
+                ++g_fwd_pingpong_seen;
+            }
+            if (rc != SWIFTK_ESHAPE) return rc;  // (SWIFTK_ESHAPE: the packed kernel is switched off by tuning key 6, nothing launched)
+        }
+        return swiftk_modnorm_residual_pair(y, d, xT, m->kd, xlo, d, lo_bits, g_, b_, mod_, ldmod, M, d, ntok, 1e-6f, stream);
+    };
     int64_t tail3[3] = {0, 0, 8};  // swiftk_gemm_tail_split_bf16's description of its walk, for the norm behind it
     int tail_rc = 0;
     for (int i = 0; i < m->depth; ++i) {
@@ -372,8 +401,7 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
         } else {
             RUN(G(att, katt, ly.wo_w, y, d, d, kav, inner, dt, SWIFTK_EPI_NONE, nullptr, nullptr, 0, (x3_exact & 2) != 0));
             if (pair)
-                RUN(swiftk_modnorm_residual_pair(y, d, xT, m->kd, xlo, d, lo_bits, ly.ln1_g, ly.ln1_b, mod + (int64_t)(2 * i) * 2 * d,
-                                                 ldmod, M, d, ntok, 1e-6f, stream));
+                RUN(PAIRNORM(ly.ln1_g, ly.ln1_b, mod + (int64_t)(2 * i) * 2 * d));
             else  // (split engine with the fused FeedForward: w1 is the only reader of this norm's output -- no fp32 operand copy)
                 RUN(NORM(y, ly.ln1_g, ly.ln1_b, mod + (int64_t)(2 * i) * 2 * d, !ff_split));
         }
@@ -419,8 +447,7 @@ extern "C" int swiftk_swinv2_forward_scaled(const swiftk_model* m, const float* 
         }
         RUN(G(hmid, m->kmlp, ly.w2_w, y, d, d, m->kmlp, m->mlp, dt, SWIFTK_EPI_NONE, nullptr, nullptr, 0, (x3_exact & 8) != 0));
         if (pair)
-            RUN(swiftk_modnorm_residual_pair(y, d, xT, m->kd, xlo, d, lo_bits, ly.ln2_g, ly.ln2_b, mod + (int64_t)(2 * i + 1) * 2 * d, ldmod,
-                                             M, d, ntok, 1e-6f, stream));
+            RUN(PAIRNORM(ly.ln2_g, ly.ln2_b, mod + (int64_t)(2 * i + 1) * 2 * d));
         else
             RUN(NORM(y, ly.ln2_g, ly.ln2_b, mod + (int64_t)(2 * i + 1) * 2 * d, true));
     }

@@ -1610,7 +1610,7 @@ static const struct { int key; int* value; } g_tuning[] = {
     {16, &g_modnorm_bwd_fused}, {17, &g_modnorm_jvp_rows}, {18, &g_x3_ffsplit}, {19, &g_fwd_pepair}, {20, &g_pp},
     {21, &g_attn_pp},         {22, &g_tn_pp},       {23, &g_fwd_rownorm},   {24, &g_rownorm_dbg},  {25, &g_zero_memset},
     {26, &g_x3_normsplit},    {27, &g_x3_qkonly},   {28, &g_x3_attnpv},     {29, &g_fwd_tail},     {30, &g_attn_sl},
-    {31, &g_gemm_sl},         {32, &g_gemm_sl_seen},
+    {31, &g_gemm_sl},         {32, &g_gemm_sl_seen},  {33, &g_fwd_pingpong}, {34, &g_fwd_pingpong_seen},
 };
 
 static int* tuning_value(int key) {
@@ -1625,7 +1625,9 @@ extern "C" int swiftk_set_tuning(int key, int value) {
         case 2: value = value > 0 ? value : 1; break;
         case 30:
         case 31: value &= 3; break;
-        case 32: value = 0; break;  // (clears; the value is ignored)
+        case 33: value = value ? 1 : 0; break;
+        case 32:
+        case 34: value = 0; break;  // (clears; the value is ignored)
         case 25: g_zero_memset = value; return (value & 4) ? swiftk_zero_check_enable() : 0;
     }
     int* const p = tuning_value(key);
