@@ -621,6 +621,29 @@ int swiftk_zonal_power(const float* x, const double* w_lat, const double* twiddl
  * (SWIFTK_ESHAPE); pred or y off a 4-byte boundary, w_lat or out off an 8-byte one (SWIFTK_EALIGN).  H and W are not restricted. */
 int swiftk_rank_histogram(const float* pred, const float* y, const double* w_lat, double* out, int n, int N, int V, int H, int W,
                           void* stream);
+/* Contingency tables of threshold events, ensemble against verifying fields (the evidence of `generate --events`: Brier score,
+ * its reliability / resolution / uncertainty decomposition and the reliability diagram all follow from the table on the host,
+ * eval/metrics.py `brier_scores`; the other verifying products score the whole distribution, this one the probability of an
+ * event -- frost, a gale, geopotential above a climatological percentile -- which lives in the tails).  The reference has none.
+ * pred [n, N, V, H, W] and y [n, V, H, W] fp32 contiguous (the layout of swiftk_rank_histogram, n lead steps of one IC),
+ * thr [E, H, W] fp32 one threshold field per event (the host broadcasts a scalar), ev_var [E] and ev_dir [E] int32 on the device:
+ * the channel of each event, and its direction -- 0: the event is x > t, nonzero: x < t.  Both comparisons are strict and IEEE: a
+ * value equal to the threshold is no event, -0 equals +0.  w_lat [H] fp64 as for swiftk_rank_histogram.  ev_var is read on the
+ * device, so it cannot be refused before the launch: the kernel clamps it into [0, V - 1] (the Python wrapper validates it).
+ * out [n, E, N + 1, 2] fp64.  For lead i, event e and a pixel (h, w) whose thr[e,h,w] is not NaN let k = #{m: event(x_m)} over
+ * the members of channel ev_var[e] and o = event(y): the pixel is counted in cell (k, o).  A pixel whose threshold is NaN is left
+ * out of every cell (the mask: sea-surface temperature over land).  NaN in pred or y is not detected, as everywhere in the
+ * metrics (it compares false: no event).
+ * Counting is exact integer work per row, c_h[k][o]; floating point enters once, in fp64: out[i,e,k,o] = the sum over h
+ * ascending of w_lat[h] * (double)c_h[k][o], product and sum rounded separately, every row a term (an empty one adds zero).  One
+ * workgroup per (i, e) plane; no float atomics, no scratch buffer, and out is written completely by every call (no clearing).
+ * The bits of a plane's table depend on (N, H, W), the weights, the threshold field and the plane's values only -- not on n, V,
+ * E, the event's position or the rank.  The cells of a plane sum to sum_h w_lat[h] #{w: thr[e,h,w] not NaN}.
+ * Refused before any launch: a null pointer or a non-positive n, N, V, H, W or E (SWIFTK_EINVAL); N > 64 or n E above 2^31 - 1
+ * (SWIFTK_ESHAPE); pred, y, thr, ev_var or ev_dir off a 4-byte boundary, w_lat or out off an 8-byte one (SWIFTK_EALIGN).  H and
+ * W are not restricted. */
+int swiftk_event_table(const float* pred, const float* y, const float* thr, const int* ev_var, const int* ev_dir,
+                       const double* w_lat, double* out, int n, int N, int V, int H, int W, int E, void* stream);
 /* Per-pixel summary of an ensemble: mean, spread and quantiles over the members (the product of `generate --summary`; the
  * reference has none -- its users dump every member and reduce the store offline).
  * pred [n, N, V, H, W] fp32 contiguous (the layout of swiftk_ensemble_sums and swiftk_rank_histogram, n lead steps of one IC),

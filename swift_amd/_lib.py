@@ -131,6 +131,7 @@ _SIGS = {
     "swiftk_sweep_sse": ([_p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "swiftk_zonal_power": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_rank_histogram": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "swiftk_event_table": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_ensemble_summary": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_ensemble_maps": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_scm_target": ([_p, _p, _p, _p, _p, _f, _f, _p, _p, _i, _l, _p], _i),

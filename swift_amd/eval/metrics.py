@@ -93,6 +93,139 @@ def rank_histogram(pred: torch.Tensor, y: torch.Tensor, lat) -> torch.Tensor:
     return out
 
 
+EVENT_OPERATORS = {"gt": 0, "lt": 1}  # the direction word of an event spec -> ev_dir of swiftk_event_table
+
+
+def parse_events(specs, file, variables, H=None, W=None):
+    """The threshold events of ``generate --events SPEC ... --events-file FILE.npz`` -> (names [E], ev_var int32 [E], ev_dir int32
+    [E], thr float32 [E, H, W]), the tables of ``swiftk_event_table`` on the host.  A spec is ``<variable>:<gt|lt>:<value>``
+    (``2m_temperature:lt:273.15``: the event is the variable strictly below 273.15); the file is an ``.npz`` (loaded with
+    ``allow_pickle=False``) whose keys are ``<variable>:<gt|lt>:<label>`` and whose values are a scalar or an [H, W] float array,
+    NaN where a pixel is to be left out (a climatological percentile field computed offline, a land mask).  The event's name is
+    the spec as typed, or the key; specs come first, then the file's keys in the file's order.  ``ValueError`` -- pure host
+    work, before any rank is started or the GPU is touched -- for an unknown variable, a bad operator, a non-finite scalar, a
+    field of the wrong shape, a duplicate name, no events at all.  Without (H, W) the field shapes are not checked (any 2-d
+    field passes) and ``thr`` is None: what the launcher can check before the dataset is open."""
+    variables = [str(v) for v in variables]
+    entries = [(str(s), None) for s in (specs or [])]
+    if file:
+        with np.load(file, allow_pickle=False) as f:
+            entries += [(str(k), np.asarray(f[k])) for k in f.files]
+    if not entries:
+        raise ValueError("events: no events given (--events <variable>:<gt|lt>:<value> ... or a non-empty --events-file)")
+    names, ev_var, ev_dir, fields = [], [], [], []
+    for name, value in entries:
+        parts = name.split(":", 2)
+        if len(parts) != 3:
+            raise ValueError(f"events: '{name}' is not <variable>:<gt|lt>:<{'label' if value is not None else 'value'}>")
+        var, op, last = parts
+        if var not in variables:
+            raise ValueError(f"events: '{name}' names the variable '{var}', which this run does not have ({', '.join(variables)})")
+        if op not in EVENT_OPERATORS:
+            raise ValueError(f"events: '{name}' has the operator '{op}', expected one of {', '.join(EVENT_OPERATORS)}")
+        if name in names:
+            raise ValueError(f"events: '{name}' is given twice")
+        if value is None:
+            try:
+                value = np.asarray(float(last))
+            except ValueError:
+                raise ValueError(f"events: '{name}' has the threshold '{last}', expected a number") from None
+        if value.dtype.kind not in "fiu":
+            raise ValueError(f"events: '{name}' holds {value.dtype} values, expected numbers")
+        if value.ndim == 0:
+            if not np.isfinite(value):
+                raise ValueError(f"events: '{name}' has the threshold {float(value)}, expected a finite number")
+        elif value.ndim != 2 or (H is not None and tuple(value.shape) != (int(H), int(W))):
+            raise ValueError(f"events: '{name}' holds a field of shape {tuple(value.shape)}, expected a scalar or "
+                             f"{[int(H), int(W)] if H is not None else '[H, W]'}")
+        names.append(name), ev_var.append(variables.index(var)), ev_dir.append(EVENT_OPERATORS[op]), fields.append(value)
+    thr = None
+    if H is not None:
+        thr = np.stack([np.broadcast_to(np.asarray(f, dtype=np.float32), (int(H), int(W))) for f in fields]).astype(np.float32)
+    return names, np.asarray(ev_var, dtype=np.int32), np.asarray(ev_dir, dtype=np.int32), thr
+
+
+def event_tables_to_device(ev_var, ev_dir, thr, V: int, device):
+    """The host tables of ``parse_events`` checked against a V-channel ensemble (``ValueError``) and put on ``device``:
+    (ev_var int32 [E], ev_dir int32 [E], thr fp32 [E, H, W]), what ``event_table`` takes call after call."""
+    ev_var, ev_dir = np.asarray(ev_var), np.asarray(ev_dir)
+    thr = np.ascontiguousarray(thr, dtype=np.float32)
+    if not (ev_var.ndim == 1 and ev_var.size > 0 and ev_var.shape == ev_dir.shape and ev_var.dtype.kind in "iu"
+            and ev_dir.dtype.kind in "iub" and thr.ndim == 3 and thr.shape[0] == ev_var.size):
+        raise ValueError(f"event_table: ev_var [E] and ev_dir [E] integers and thr [E, H, W] expected, got {ev_var.dtype} "
+                         f"{ev_var.shape}, {ev_dir.dtype} {ev_dir.shape} and {thr.shape}")
+    if ev_var.min() < 0 or ev_var.max() >= V:
+        raise ValueError(f"event_table: ev_var {ev_var.tolist()} outside the {V} channels")
+    return (torch.from_numpy(ev_var.astype(np.int32)).to(device), torch.from_numpy((ev_dir != 0).astype(np.int32)).to(device),
+            torch.from_numpy(thr).to(device))
+
+
+def event_table(pred: torch.Tensor, y: torch.Tensor, lat, ev_var, ev_dir, thr) -> torch.Tensor:
+    """Latitude-weighted contingency tables of threshold events (definition: include/swiftk.h, ``swiftk_event_table``: a pixel
+    with k members in the event and outcome o adds w_lat[h] to cell (k, o); a NaN threshold leaves the pixel out).  pred [n, N,
+    V, H, W], y [n, V, H, W], fp32 on the device -> [n, E, N + 1, 2] fp64 on the device.  ``ev_var`` / ``ev_dir`` [E] and ``thr``
+    [E, H, W] as host arrays (``parse_events``) are checked against V here and uploaded; given as device tensors (int32, int32,
+    fp32: ``event_tables_to_device``, once per job) they are taken as they are -- reading them back would stall the stream --
+    and the kernel clamps a channel outside [0, V - 1]."""
+    if not (isinstance(pred, torch.Tensor) and isinstance(y, torch.Tensor) and pred.is_cuda and y.is_cuda and pred.ndim == 5
+            and y.ndim == 4 and pred.dtype == torch.float32 and y.dtype == torch.float32 and y.device == pred.device
+            and tuple(y.shape) == (pred.shape[0],) + tuple(pred.shape[2:]) and 1 <= pred.shape[1] <= 64 and pred.numel() > 0):
+        raise ValueError(f"event_table: fp32 device pred [n, N, V, H, W] with N <= 64 and y [n, V, H, W] expected, got "
+                         f"{getattr(pred, 'dtype', type(pred))} {tuple(getattr(pred, 'shape', ()))} on {getattr(pred, 'device', None)} "
+                         f"and {getattr(y, 'dtype', type(y))} {tuple(getattr(y, 'shape', ()))} on {getattr(y, 'device', None)}")
+    n, N, V, H, W = pred.shape
+    if not all(isinstance(t, torch.Tensor) for t in (ev_var, ev_dir, thr)):
+        ev_var, ev_dir, thr = event_tables_to_device(ev_var, ev_dir, thr, V, pred.device)
+    E = ev_var.numel()
+    if not (ev_var.dtype == torch.int32 and ev_dir.dtype == torch.int32 and thr.dtype == torch.float32 and E > 0
+            and ev_var.ndim == 1 and tuple(ev_dir.shape) == (E,) and tuple(thr.shape) == (E, H, W)
+            and ev_var.device == ev_dir.device == thr.device == pred.device):
+        raise ValueError(f"event_table: int32 ev_var [E], int32 ev_dir [E] and fp32 thr [E, {H}, {W}] on {pred.device} expected, got "
+                         f"{ev_var.dtype} {tuple(ev_var.shape)}, {ev_dir.dtype} {tuple(ev_dir.shape)}, {thr.dtype} {tuple(thr.shape)} "
+                         f"on {thr.device}")
+    pred, y, ev_var, ev_dir, thr = pred.contiguous(), y.contiguous(), ev_var.contiguous(), ev_dir.contiguous(), thr.contiguous()
+    w_lat, _ = _spectrum_tables(W, lat, pred.device)   # the fp64 weights of the spectra (the twiddle table rides along unused)
+    if w_lat.numel() != H:
+        raise ValueError(f"event_table: {w_lat.numel()} latitudes for {H} rows")
+    out = torch.empty(n, E, N + 1, 2, dtype=torch.float64, device=pred.device)  # written completely by every call
+    check(lib().swiftk_event_table(pred.data_ptr(), y.data_ptr(), thr.data_ptr(), ev_var.data_ptr(), ev_dir.data_ptr(),
+                                   w_lat.data_ptr(), out.data_ptr(), n, N, V, H, W, E, torch.cuda.current_stream().cuda_stream),
+          "swiftk_event_table")
+    return out
+
+
+BRIER_SCORES = ["brier", "fair_brier", "reliability", "resolution", "uncertainty", "bss", "base_rate"]
+
+
+def brier_scores(table, members: int) -> Dict[str, np.ndarray]:
+    """Brier score and its decomposition from contingency tables [..., E, N + 1, 2] (``event_table``, or any positive multiple of
+    sums of them) -> {score: [..., E] fp64}, pure host code.  With n_k = T[k,0] + T[k,1], o_k = T[k,1], p_k = k / N, S = sum n_k:
+    ``base_rate`` = sum o_k / S; ``brier`` = sum [o_k (1 - p_k)^2 + (n_k - o_k) p_k^2] / S; ``reliability`` = sum n_k (p_k -
+    o_k / n_k)^2 / S and ``resolution`` = sum n_k (o_k / n_k - base_rate)^2 / S over the non-empty bins; ``uncertainty`` =
+    base_rate (1 - base_rate); ``fair_brier`` = brier - sum n_k k (N - k) / (N^2 (N - 1)) / S (Ferro's ensemble-size correction:
+    NaN for one member); ``bss`` = 1 - brier / uncertainty, NaN where the uncertainty is 0.  The forecast takes exactly the
+    N + 1 values p_k, so brier = reliability - resolution + uncertainty holds exactly in real arithmetic.  A table without any
+    pixel (an all-NaN threshold field) gives NaN everywhere, without a warning."""
+    T = np.asarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table, dtype=np.float64)
+    N = int(members)
+    if N < 1 or T.ndim < 2 or T.shape[-2:] != (N + 1, 2):
+        raise ValueError(f"brier_scores: tables [..., {N + 1}, 2] of {N} >= 1 members expected, got {T.shape}")
+    n_k, o_k = T[..., 0] + T[..., 1], T[..., 1]
+    k = np.arange(N + 1, dtype=np.float64)
+    p, S = k / N, n_k.sum(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        base = o_k.sum(-1) / S
+        brier = (o_k * (1.0 - p) ** 2 + (n_k - o_k) * p ** 2).sum(-1) / S
+        obar = o_k / n_k
+        full = n_k > 0
+        rel = np.where(full, n_k * (p - obar) ** 2, 0.0).sum(-1) / S
+        res = np.where(full, n_k * (obar - base[..., None]) ** 2, 0.0).sum(-1) / S
+        unc = base * (1.0 - base)
+        fair = brier - (n_k * k * (N - k)).sum(-1) / (float(N) ** 2 * (N - 1)) / S if N >= 2 else np.full(S.shape, np.nan)
+        bss = np.where(unc > 0, 1.0 - brier / unc, np.nan)
+    return dict(brier=brier, fair_brier=fair, reliability=rel, resolution=res, uncertainty=unc, bss=bss, base_rate=base)
+
+
 MAX_QUANTILES = 16  # what swiftk_ensemble_summary takes in one call
 
 

@@ -35,7 +35,13 @@ them and loads no verifying fields: ``--dump none --summary`` is a complete job)
 ``evaluation_maps.zarr`` and ``evaluation_regions.json``: per lead step, variable and grid point the bias, MSE, fair CRPS and
 member variance, means over the ICs -- ``swiftk_ensemble_maps`` in fp64 on the device, accumulated per rank in one resident
 buffer -- and their latitude-weighted means over the globe, the tropics and the two extratropics: where the forecast is good,
-which no whole-grid average can tell) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
+which no whole-grid average can tell), ``--events SPEC ... [--events-file FILE.npz]`` (either implies ``--metrics``; adds
+``evaluation_reliability.npz`` and ``evaluation_brier.json``: for every threshold event -- ``2m_temperature:lt:273.15``, or a
+per-grid-point threshold field from the file, NaN where a pixel is left out -- and lead step the latitude-weighted contingency
+table of the number of members in the event against the outcome, ``swiftk_event_table`` in exact integers and fp64 on the device,
+and from it the reliability diagram, the Brier score with its reliability / resolution / uncertainty decomposition, the fair
+Brier score and the skill score against climatology: the probability of an event, which lives in the tails where a score of the
+whole distribution looks least) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
 """
 from __future__ import annotations
 
@@ -52,7 +58,7 @@ import torch.distributed as tdist
 
 from . import dist
 from .config import Cfg, instantiate, load_saved
-from .eval.metrics import MAP_STATISTICS, quantile_table, region_means, scores_from_sums
+from .eval.metrics import BRIER_SCORES, MAP_STATISTICS, brier_scores, parse_events, quantile_table, region_means, scores_from_sums
 from .rollout import RolloutEngine, unit_seed
 from .utils import zarrlite
 
@@ -94,6 +100,12 @@ parser.add_argument("--summary", action="store_true", help="per IC, lead step, v
 parser.add_argument("--maps", action="store_true", help="implies --metrics; per lead step, variable and grid point the bias, MSE, "
                     "fair CRPS and member variance, means over the ICs -> evaluation_maps.zarr, and their regional means "
                     "(global, tropics, extratropics) -> evaluation_regions.json")
+parser.add_argument("--events", type=str, nargs="+", default=None, metavar="SPEC", help="implies --metrics; threshold events "
+                    "<variable>:<gt|lt>:<value> (2m_temperature:lt:273.15): per lead step the contingency table of members in the "
+                    "event against the outcome -> evaluation_reliability.npz, and the Brier score, its decomposition and the skill "
+                    "score -> evaluation_brier.json")
+parser.add_argument("--events-file", type=str, default=None, metavar="FILE.npz", help="implies --metrics; further events: keys "
+                    "<variable>:<gt|lt>:<label>, values a scalar or an [H, W] threshold field, NaN where a pixel is left out")
 parser.add_argument("--quantiles", type=float, nargs="+", default=[0.1, 0.5, 0.9], help="quantiles of --summary, each in [0, 1], "
                     "at most 16 (default: 0.1 0.5 0.9)")
 
@@ -377,6 +389,54 @@ def collect_maps(local, steps, n_ic, members, variables, lat, lon, interval, odi
     return regions
 
 
+RELIABILITY_FILE, BRIER_FILE = "evaluation_reliability.npz", "evaluation_brier.json"
+
+
+def check_events_args(args, cfg=None):
+    """``--events`` / ``--events-file`` checked on the host (``ValueError``), before any rank is started or the GPU is touched:
+    2 .. 64 members, and ``parse_events`` against the variables (and, where it names one, the grid) of the run's saved config."""
+    if getattr(args, "events", None) or getattr(args, "events_file", None):
+        if not 2 <= args.members <= 64:
+            raise ValueError(f"--events takes the event probability from 2 .. 64 members, got --members {args.members}")
+        ds = (cfg if cfg is not None else load_cfg(args)).data.dataset
+        parse_events(args.events, args.events_file, ds.variables, *(ds.get("img_resolution") or (None, None)))
+
+
+def collect_events(local, n_ic, members, names, variables, interval, odir):
+    """``local`` [steps, E, members + 1, 2] fp64: this rank's sums over its ICs of the ``event_table`` cells (the ``Events``
+    product's).  One all-gather of these arrays (never of per-IC rows), rank 0 adds them in rank order and writes
+    ``evaluation_reliability.npz`` (plain arrays, no pickles): events [E], variables [E] (each event's variable), lead_hours
+    [steps], probability [members + 1] = k / members, forecast_frequency [steps, E, members + 1] = n_k / S (each row sums to 1),
+    observed_frequency [steps, E, members + 1] = o_k / n_k (NaN in an empty bin), table [steps, E, members + 1, 2] the summed cells
+    divided by ``n_ic``, members, samples -- and ``evaluation_brier.json``: ``brier_`` / ``fair_brier_`` / ``reliability_`` /
+    ``resolution_`` / ``uncertainty_`` / ``bss_`` / ``base_rate_<event>_<lead>h`` (``eval.metrics.brier_scores`` of the table),
+    NaN written as null."""
+    total = dist.sum_in_rank_order(local)
+    if total is None:
+        return None
+    steps, E, bins, _ = total.shape
+    assert bins == members + 1 and E == len(names) == len(variables)
+    table = total / float(n_ic)
+    n_k = table[..., 0] + table[..., 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        arrays = dict(events=np.array([str(e) for e in names], dtype=np.str_),
+                      variables=np.array([str(v) for v in variables], dtype=np.str_),
+                      lead_hours=(np.arange(steps, dtype=np.int64) + 1) * int(interval),
+                      probability=np.arange(bins, dtype=np.float64) / members,
+                      forecast_frequency=n_k / n_k.sum(-1, keepdims=True), observed_frequency=table[..., 1] / n_k, table=table,
+                      members=np.int64(members), samples=np.int64(n_ic))
+    path, jpath = os.path.join(odir, RELIABILITY_FILE), os.path.join(odir, BRIER_FILE)
+    np.savez(path, allow_pickle=False, **arrays)
+    scores = brier_scores(table, members)                                 # {score: [steps, E]}
+    flat = {f"{s}_{e}_{(j + 1) * interval}h": (float(scores[s][j, i]) if np.isfinite(scores[s][j, i]) else None)
+            for j in range(steps) for i, e in enumerate(names) for s in BRIER_SCORES}
+    with open(jpath, "w") as f:
+        json.dump(flat, f, indent=1)
+    dist.log0(f"threshold events (--events) of {n_ic} ICs x {members} members, {E} events at {steps} lead steps, gathered from "
+              f"{dist.get_world_size()} rank(s): reliability diagrams {path}; Brier scores {jpath}")
+    return arrays
+
+
 def load_cfg(args) -> Cfg:
     """The run's saved composed config (generate.py:161), or the synthetic one when ``--synthetic`` names no run directory."""
     if args.synthetic and not os.path.exists(os.path.join(args.input, ".hydra", "config.yaml")):
@@ -422,6 +482,7 @@ def main(args):
     check_summary_args(args)
     check_maps_args(args)
     cfg = load_cfg(args)
+    check_events_args(args, cfg)
     solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
     dist.setup_torch(backend=cfg.system.torch.backend)
     np.random.seed(cfg.seed % (1 << 31))
@@ -436,7 +497,7 @@ def main(args):
     net, ckpt_basename = build_net(cfg, dataset, args, device)
 
     from .generating.products import MetricSums, product_types
-    args.metrics = MetricSums in product_types(args)  # (--spectra, --rank-hist and --maps imply the metric sums)
+    args.metrics = MetricSums in product_types(args)  # (--spectra, --rank-hist, --maps and --events imply the metric sums)
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
         if args.dump == "none":
@@ -491,5 +552,6 @@ if __name__ == "__main__":
     _args = parser.parse_args()
     check_summary_args(_args)
     check_maps_args(_args)
+    check_events_args(_args)
     dist.maybe_launch_ranks(_args.gpus, "swift_amd.generate")  # before anything touches the GPU; returns in the ranks
     main(_args)

@@ -169,6 +169,26 @@ class Maps(Product):
                               self.interval, self.odir, self.device)
 
 
+class Events(Product):
+    """--events / --events-file: an IC's contingency tables [steps, E, members + 1, 2] fp64 on the device, the cells of an
+    (event, lead) table summing to the sum over the rows of w_lat[h] times the row's unmasked pixels.  The events are parsed on the host when the
+    product is made; their tables go to the device with the first IC."""
+
+    def __init__(self, *job, specs, file):
+        super().__init__(*job)
+        self.names, self.ev_var, self.ev_dir, self.thr = metrics.parse_events(specs, file, self.variables, *self.dataset.img_resolution)
+        self.tables = None
+
+    def add_ic(self, ic, traj, pred, y):
+        if self.tables is None:
+            self.tables = metrics.event_tables_to_device(self.ev_var, self.ev_dir, self.thr, self.nv, pred.device)
+        self.add(metrics.event_table(pred, y.contiguous(), self.lat, *self.tables))
+
+    def finish(self):
+        generate.collect_events(self.local(self.steps, len(self.names), self.members + 1, 2), self.n_ic, self.members, self.names,
+                                [str(self.variables[v]) for v in self.ev_var], self.interval, self.odir)
+
+
 class Summary(Product):
     """--summary: swiftk_ensemble_summary of the IC's members at every lead step, lead 0 included.  The [steps + 1, 2 + Q, nv, H,
     W] result stays on the device until the summary thread has taken it -- through one pinned buffer on a stream of its own -- and
@@ -212,8 +232,10 @@ class Summary(Product):
 
 
 def product_types(args) -> list:
-    """The product classes of a command line, in feeding order: --spectra, --rank-hist and --maps imply the metric sums."""
+    """The product classes of a command line, in feeding order: --spectra, --rank-hist, --maps and --events / --events-file imply
+    the metric sums."""
     implying = [c for c, flag in ((Spectra, "spectra"), (RankHistogram, "rank_hist"), (Maps, "maps")) if getattr(args, flag, False)]
+    implying += [Events] if getattr(args, "events", None) or getattr(args, "events_file", None) else []
     truth = [MetricSums] + implying if implying or getattr(args, "metrics", False) else []
     return truth + ([Summary] if getattr(args, "summary", False) else [])
 
@@ -221,7 +243,8 @@ def product_types(args) -> list:
 def products_from_args(args, dataset, members, steps, ofile, device, n_ic=None, interval=6, loaders=None) -> list:
     job = (dataset, members, steps, n_ic, interval, device, os.path.dirname(ofile))  # what every product of a job knows
     summary = dict(quantiles=getattr(args, "quantiles", None), ofile=ofile, loaders=loaders, ics_per_batch=max(1, int(args.batch) // members))
-    return [c(*job, **(summary if c is Summary else {})) for c in product_types(args)]
+    own = {Summary: summary, Events: dict(specs=getattr(args, "events", None), file=getattr(args, "events_file", None))}
+    return [c(*job, **own.get(c, {})) for c in product_types(args)]
 
 
 def plan_units(products, n_ic, members, batch, rank, world):
