@@ -855,6 +855,7 @@ typedef struct swiftk_model {
  * the torch.optim.Adam / AdamW update (torch/optim/adam.py single-tensor rule) and the EMA rule
  * p_ema <- p_net.lerp(p_ema, ema_beta).  `chunks` is a DEVICE table, one entry per <= 16384 consecutive elements of one
  * parameter tensor; gradients and both moments are flat fp32 buffers indexed by flat_off.  `hyper_host` is read on the host.
+ * Returns SWIFTK_EINVAL before anything is launched for a NULL pointer or n_chunks <= 0.
  */
 #define SWIFTK_OPT_MAX_GROUPS 8
 typedef struct {
@@ -868,7 +869,9 @@ typedef struct {
     float lr[SWIFTK_OPT_MAX_GROUPS];
     float weight_decay[SWIFTK_OPT_MAX_GROUPS];
     float step_size[SWIFTK_OPT_MAX_GROUPS]; /* lr / (1 - beta1^t)                      */
-    float beta1, beta2, eps;
+    float beta1, one_minus_beta1;           /* 1 - beta rounded from the double on the host, as torch rounds it: */
+    float beta2, one_minus_beta2;           /* 1.0f - (float)0.999 is 4.7e-5 away from (float)0.001              */
+    float eps;
     float bias2_sqrt;                       /* sqrt(1 - beta2^t)                        */
     float ema_beta;
     int32_t decoupled;                      /* 1: AdamW (p *= 1 - lr wd), 0: Adam (g += wd p) */

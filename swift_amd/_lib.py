@@ -46,8 +46,9 @@ class OptChunk(C.Structure):
 
 class OptHyper(C.Structure):
     _fields_ = [("lr", C.c_float * OPT_MAX_GROUPS), ("weight_decay", C.c_float * OPT_MAX_GROUPS),
-                ("step_size", C.c_float * OPT_MAX_GROUPS), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
-                ("bias2_sqrt", C.c_float), ("ema_beta", C.c_float), ("decoupled", C.c_int32)]
+                ("step_size", C.c_float * OPT_MAX_GROUPS), ("beta1", C.c_float), ("one_minus_beta1", C.c_float),
+                ("beta2", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float), ("bias2_sqrt", C.c_float),
+                ("ema_beta", C.c_float), ("decoupled", C.c_int32)]
 
 
 MARS_ADAMW, MARS_LION = 0, 1

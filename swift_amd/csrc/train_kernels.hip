@@ -996,6 +996,9 @@ __global__ __launch_bounds__(256) void ensemble_sums_kernel(const float* __restr
 // p_ema and writes p, m, v, p_ema (36 B per parameter) where the reference runs nan_to_num, ~10 _foreach passes of
 // torch.optim.AdamW and a lerp per tensor.  Work arrives as a chunk table (one block per <= 16384-element chunk of one
 // parameter tensor): parameters and EMA copies stay ordinary separately-allocated tensors, gradients and moments are flat.
+static_assert(sizeof(swiftk_opt_chunk) == 32 && sizeof(swiftk_opt_hyper) == 4 * (3 * SWIFTK_OPT_MAX_GROUPS + 8),
+              "swift_amd/_lib.py mirrors these layouts");
+
 __global__ __launch_bounds__(256) void adamw_ema_kernel(const swiftk_opt_chunk* __restrict__ chunks, float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, swiftk_opt_hyper h) {
     const swiftk_opt_chunk c = chunks[blockIdx.x];
@@ -1013,8 +1016,8 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const swiftk_opt_chunk* 
         float pi = p[i] * decay;
         gi += l2 * pi;                                   // Adam (not W): L2 term joins the gradient
         float mi = m[c.flat_off + i], vi = v[c.flat_off + i];
-        mi += (gi - mi) * (1.0f - h.beta1);              // exp_avg.lerp_(grad, 1 - beta1)
-        vi = vi * h.beta2 + (1.0f - h.beta2) * gi * gi;
+        mi += (gi - mi) * h.one_minus_beta1;             // exp_avg.lerp_(grad, 1 - beta1); the weights come rounded from the
+        vi = vi * h.beta2 + h.one_minus_beta2 * gi * gi;  // host's doubles: 1.0f - h.beta2 is 1.3e-5 off at beta2 = 0.999
         const float denom = sqrtf(vi) / h.bias2_sqrt + h.eps;
         pi -= step_size * (mi / denom);
         p[i] = pi;
@@ -1099,21 +1102,27 @@ struct mars_coef {
     bool adam;                       // false: lion (sign of the first moment; the second moment is not touched)
 };
 
+// Every multiply-add below is spelled out and nothing else may be contracted: the 16-byte and the dword loop of
+// mars_update_kernel inline this function separately, and left to itself the compiler fuses different pairs in the two, so
+// the same element got different bits depending on the alignment of its chunk.
 __device__ __forceinline__ void mars_elem(const mars_coef& q, float g, float lg, float& m, float& v, float& p) {
+#pragma clang fp contract(off)
     const float c = mars_c(g, lg, q.k) * q.scale;
-    m = m * q.b1 + q.omb1 * c;
+    m = fmaf(m, q.b1, q.omb1 * c);
     float dir;
     if (q.adam) {
-        v = v * q.b2 + q.omb2 * c * c;
-        dir = m / ((sqrtf(v) * q.inv_b2s + q.eps) * q.bias1);
+        v = fmaf(v, q.b2, (q.omb2 * c) * c);
+        dir = m / (fmaf(sqrtf(v), q.inv_b2s, q.eps) * q.bias1);
     } else {
         dir = (float)(m > 0.0f) - (float)(m < 0.0f);
     }
-    p += q.neg_lr * (p * q.wd + dir);
+    p = fmaf(q.neg_lr, fmaf(p, q.wd, dir), p);
 }
 
-__device__ __forceinline__ float ema_lerp(const mars_coef& q, float e, float p) {  // torch's two-sided lerp, as adamw_ema_kernel
-    return q.ema_beta < 0.5f ? p + q.ema_beta * (e - p) : e - (e - p) * q.omb;
+// torch's two-sided lerp, as adamw_ema_kernel; exact at ema_beta 0 (p) and 1 (e)
+__device__ __forceinline__ float ema_lerp(const mars_coef& q, float e, float p) {
+#pragma clang fp contract(off)
+    return q.ema_beta < 0.5f ? fmaf(q.ema_beta, e - p, p) : fmaf(p - e, q.omb, e);
 }
 
 __global__ __launch_bounds__(256) void mars_update_kernel(const swiftk_mars_chunk* __restrict__ chunks,

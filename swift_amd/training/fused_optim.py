@@ -132,6 +132,7 @@ class FusedAdamEMA:
             h.lr[gi], h.weight_decay[gi] = float(g["lr"]), float(g["weight_decay"])
             h.step_size[gi] = float(g["lr"]) / (1.0 - b1 ** t)
         h.beta1, h.beta2, h.eps = float(b1), float(b2), float(g0["eps"])
+        h.one_minus_beta1, h.one_minus_beta2 = 1.0 - b1, 1.0 - b2  # rounded from the double, as torch's lerp_ / addcmul_ weights
         h.bias2_sqrt = (1.0 - b2 ** t) ** 0.5
         h.ema_beta = float(ema_beta)
         h.decoupled = int(self.decoupled)
