@@ -552,7 +552,9 @@ int swiftk_modnorm_jvp_pair(const void* y, const void* dy, int64_t ldy, const vo
  *       primal pre-activations (the saved activation of SWIFTK_EPI_SWIGLU_BWD). */
 int swiftk_gemm_jvp(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t Mh, int64_t N, int64_t K,
                     int epilogue, const float* scale, float* rn, int head_dim, void* C2, int64_t ldc2, void* stream);
-/* SwiGLU and its tangent on interleaved (gate_j, up_j) columns (swinv2.py:99-100). */
+/* SwiGLU and its tangent on interleaved (gate_j, up_j) columns (swinv2.py:99-100).  bf16 storage: the tangent, a sum of two
+ * products that can cancel, is formed in fp64 and converted from fp64 to bf16 directly (one rounding of the exact value, not a
+ * second one through fp32), the primal in fp32; fp32 storage: fp32 throughout. */
 int swiftk_swiglu_jvp(const void* h, const void* dh, int64_t ldh, void* out, void* dout, int64_t ldo, int64_t M, int mlp,
                       int dtype, void* stream);
 /* sCM regression target (loss.py:236-247): g = -cos^2 t (sd F - dxt) - r (cos t sin t x_t + sd dF), g /= (rms_b(g) + 0.1),

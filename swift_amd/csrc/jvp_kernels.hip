@@ -97,6 +97,25 @@ __global__ __launch_bounds__(256) void qknorm_jvp_kernel(T* __restrict__ qkv, T*
 
 // --------------------------------------------------------------------------------- SwiGLU tangent
 // h [M, 2*mlp] with columns interleaved (gate_j, up_j):  o = silu(g) u,  do = silu'(g) dg u + silu(g) du
+// The tangent is a SUM of two products, and the two cancel: to 2.5e-6 of their size at one of the 1.1 M elements of
+// tests/test_gpu_tangent_kernels.py (test_swiglu_jvp_alone), below 2^-15 at twenty.  An fp32 evaluation carries 1e-7 of the TERMS
+// (the sigmoid alone), which is then 2 bf16 ulp of such a result.  fp32 results are held to the error of an fp32 evaluation and keep
+// it; bf16 results are held to one ulp of the rounded exact value, so their tangent is formed in fp64 (sigmoid included) and
+// converted from fp64 to bf16 DIRECTLY: one rounding.  (Through fp32 it would be two, and with bf16 operands the exact value often
+// lies within 2^-24 of a bf16 tie, which the fp32 step then lands on: 11 of the 1.1 M test elements.)
+// Cost: an fp64 exp and division per element in the bf16 instantiation, which the engine takes whenever the fused swiftk_gemm_jvp
+// does not apply (rows not a multiple of 128, an odd head count, mlp % 8 != 0, SWIFTK_JVP_UNFUSED); measured in
+// test_swiglu_jvp_alone's docstring.
+template <typename T>
+__device__ __forceinline__ T swiglu_tangent(float g, float u, float dg, float du, float s) {
+    if constexpr (sizeof(T) == 4) {
+        return (s + g * s * (1.0f - s)) * dg * u + g * s * du;
+    } else {
+        const double gd = g, sd = 1.0 / (1.0 + exp(-gd));
+        const double t = (sd + gd * sd * (1.0 - sd)) * ((double)dg * (double)u) + gd * sd * (double)du;
+        return __builtin_bit_cast(bf16_t, (__bf16)t);
+    }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_jvp_kernel(const T* __restrict__ h, const T* __restrict__ dh, int64_t ldh,
                                                          T* __restrict__ o, T* __restrict__ dout, int64_t ldo, int64_t M,
@@ -109,7 +128,7 @@ __global__ __launch_bounds__(256) void swiglu_jvp_kernel(const T* __restrict__ h
         const float dg = ldf(dh + m * ldh + 2 * j), du = ldf(dh + m * ldh + 2 * j + 1);
         const float s = 1.0f / (1.0f + expf(-g));
         o[m * ldo + j] = elem<T>::from_f(g * s * u);
-        dout[m * ldo + j] = elem<T>::from_f((s + g * s * (1.0f - s)) * dg * u + g * s * du);
+        dout[m * ldo + j] = swiglu_tangent<T>(g, u, dg, du, s);
     }
 }
 

@@ -1,6 +1,6 @@
 """Inputs with ONE right answer for the window-attention family: builders, CPU references and the case table (no GPU here).
 
-Two input families make softmax(q k^T) v independent of how a kernel rounds, orders or normalises:
+Three input families make softmax(q k^T) v (the third: and its tangent) independent of how a kernel rounds, orders or normalises:
 
   selector  one-hot softmax.  Per (sample, window, head) item the 256 keys are random +-1 code vectors (largest off-diagonal |cos|
             <= COS_CAP, a seeded retry loop) times a positive magnitude; query i is the code of key pi(i) for a random permutation pi
@@ -14,6 +14,16 @@ Two input families make softmax(q k^T) v independent of how a kernel rounds, ord
             logit, the column sum S is an integer of magnitude <= 256 (every partial sum too) and S / 256 is a bf16 value: one bit
             pattern whether the kernel divides, multiplies by a reciprocal, subtracts a maximum or not.  Pins "every key is summed
             exactly once" in both softmax forms, which the selector cannot see.
+
+  flat      the tangent entry (swiftk_window_attention_jvp) with q, k, dq, dk, v, dv ALL nonzero, which neither family above can
+            give it.  Per item a set A of FLAT_A coordinates is drawn; every key holds 1 on A and ternary values elsewhere; query i
+            is s_i e_{a_i} with a_i in A and s_i in {1, 2, 4}, so every logit of row i is s_i: e = 1, l = 256, P = 2^-8, while the
+            query rows still differ.  dq_i and dk_j hold four +-1 each at random places: dS = dQ K^T + Q dK^T is an integer with
+            |dS| <= 8, so W = e o dS is a bf16 value; v and dv hold integers in [-2, 2].  Then
+                out = colsum(v) / 256,    dout = (256 (W V + 1 dV) - r (1 V)) / 65536,   r = rowsum(W),
+            every accumulation a sum of integers far below 2^24 (exact in any order), and the kernels' fp32 sequence
+            ((u + tt) - (r rl) o) rl is exact as well: 256 x the bracket is an integer below 2^24.  The fp32 kernel must return the
+            value, the bf16 kernel its RNE rounding.  tests/test_exact_attention_cpu.py proves each of these for every row.
 
 For swiftk_qkv_attention_fused (and swiftk_gemm_qkv_tiled) q / k / v are PRODUCTS, so the structure goes into x and W
 (`fused_operands`): x has +-1 entries, block h of a token's row is base[sigma_h(i)], W_k of head h selects block h, W_q block h + 1,
@@ -404,6 +414,61 @@ def uniform_backward(c: Case):
     g = torch.Generator().manual_seed(c.seed + 4)
     do = ternary(u["v"].shape, g)
     return dict(do=do, dv=(do.sum(dim=3, keepdim=True) / 256).expand_as(do).contiguous())
+
+
+# ------------------------------------------------------------------------------------------------ the tangent entry: flat
+FLAT_A = 4                                    # coordinates of an item's set A
+
+
+@lru_cache(maxsize=2)
+def flat(c: Case):
+    """dict of window-order tensors q, k, v, dq, dk, dv [B, nW, H, 256, hd] (small integers: one tensor serves both storage types)
+    and the set A [B, nW, H, FLAT_A] (module docstring, "flat")."""
+    g = torch.Generator().manual_seed(c.seed + 20)
+    sh = (c.B, c.nW, c.heads)
+    full = (*sh, 256, c.hd)
+    A = torch.rand(*sh, c.hd, generator=g).argsort(-1)[..., :FLAT_A]
+    k = ternary(full, g).scatter_(-1, A.unsqueeze(-2).expand(*sh, 256, FLAT_A).contiguous(), 1.0)
+    a = A.gather(-1, torch.randint(0, FLAT_A, (*sh, 256), generator=g))                       # a_i in A
+    s = torch.tensor([1.0, 2.0, 4.0])[torch.randint(0, 3, (*sh, 256), generator=g)]
+    q = torch.zeros(full).scatter_(-1, a.unsqueeze(-1), s.unsqueeze(-1))
+
+    def four_signs():
+        pos = torch.rand(full, generator=g).argsort(-1)[..., :4]
+        return torch.zeros(full).scatter_(-1, pos, torch.randint(0, 2, (*sh, 256, 4), generator=g).float() * 2 - 1)
+
+    dq, dk = four_signs(), four_signs()
+    v, dv = (torch.randint(-2, 3, full, generator=g).float() for _ in range(2))
+    return dict(q=q, k=k, v=v, dq=dq, dk=dk, dv=dv, A=A)
+
+
+def flat_expected(c: Case, zero=()):
+    """The closed form of the flat family in fp64 (every value an integer / 2^16, exact), one sample at a time:
+    out = colsum(v) / 256, dout = (256 (dS V + 1 dV) - r (1 V)) / 65536 with dS = dQ K^T + Q dK^T and r = rowsum(dS).
+    ``zero``: names among dq, dk, dv taken as zero.  Returns dict(out, dout [B, nW, H, 256, hd] fp64, ds_max = max |dS|,
+    budget = the largest sum of ABSOLUTE terms of any accumulation, in units of the result's last place: the integers behind S, dS,
+    l, r, 1 V, dS V, 1 dV in units of 1 and the final numerator in units of 2^-16)."""
+    f = flat(c)
+    outs, douts, ds_max, budget = [], [], 0.0, 0.0
+    for b in range(c.B):
+        q, k, v, dq, dk, dv = (torch.zeros_like(f[n][b]).double() if n in zero else f[n][b].double() for n in ("q", "k", "v", "dq", "dk", "dv"))
+        kt = k.transpose(-2, -1)
+        ds = dq @ kt + q @ dk.transpose(-2, -1)
+        r = ds.sum(-1, keepdim=True)
+        o = v.sum(-2, keepdim=True)
+        douts.append((256.0 * (ds @ v + dv.sum(-2, keepdim=True)) - r * o) / 65536.0)
+        outs.append((o / 256.0).expand_as(v).contiguous())
+        ds_max = max(ds_max, float(ds.abs().max()))
+        abs_ds = dq.abs() @ kt.abs() + q.abs() @ dk.abs().transpose(-2, -1)                   # sum of |terms| behind every dS
+        numer = 256.0 * (abs_ds @ v.abs() + dv.abs().sum(-2, keepdim=True)) + abs_ds.sum(-1, keepdim=True) * v.abs().sum(-2, keepdim=True)
+        budget = max(budget, float(numer.max()), float((q.abs() @ kt.abs()).max()), float(abs_ds.sum(-1).max()))
+    return dict(out=torch.stack(outs), dout=torch.stack(douts), ds_max=ds_max, budget=budget)
+
+
+def flat_qkv(c: Case):
+    """token-order (qkv, dqkv) [B, n, 3 dim] fp32 of the flat family."""
+    f = flat(c)
+    return assemble(c, f["q"], f["k"], f["v"]), assemble(c, f["dq"], f["dk"], f["dv"])
 
 
 def sent(shape, f32, device="cpu"):

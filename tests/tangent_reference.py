@@ -6,6 +6,7 @@ tests/test_gpu_tangent_kernels.py checks one by one.
   * ``modnorm_tangent_fp32``   -- the same formula in fp32, two-pass and in the one-pass shifted form of the 32-rows-per-block
                                   pair kernel: the yardstick of the GPU tolerances (a restatement of the mathematics)
   * ``pair_quantise``          -- the value a (bf16 hi, 8-bit lo) pair holds for an fp32 value (csrc/common.h: lo8_insert)
+  * ``qknorm_tangent``, ``swiglu_tangent`` -- swiftk_qknorm_jvp / swiftk_swiglu_jvp standing alone, with their input builders
   * ``silu_tangent`` / ``silu_grad``, ``timestep_embed_tangent``, ``scm_target``, ``rmse_sums`` -- small closed forms
   * ``make_norm_case``         -- seeded inputs of the norm tests with four hostile rows
 
@@ -13,6 +14,8 @@ tests/test_tangent_reference_cpu.py pins every one of them to ``torch.func.jvp``
 asserts that each additive term of the tangent is a visible share of the whole on these inputs.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -107,6 +110,76 @@ def silu_tangent(z: torch.Tensor, dz: torch.Tensor):
     """(silu(z), silu'(z) dz) in fp64."""
     z = z.double()
     return z * torch.sigmoid(z), silu_grad(z) * dz.double()
+
+
+LN100 = math.log(100.0)
+QKNORM_JVP_CASES = ((3, 3, 80), (3, 3, 88), (3, 3, 96), (129, 12, 88))   # (M, heads, head_dim): 18 vectors (one ragged block), 3096 (193.5)
+
+
+def qknorm_tangent(qkv, dqkv, scale, heads, hd, dtype=torch.float64):
+    """What swiftk_qknorm_jvp leaves for qkv, dqkv [M, heads * 3 * hd] (columns head-major, then q | k | v):
+    x-hat = tau x / n,  d x-hat = tau / n (dx - x (x . dx) / n^2),  n = max(|x|, 1e-12),  tau = exp(min(scale_h, ln 100)) for q and 1
+    for k; v and dv pass through.  Returns (qkvh, dqkvh [M, heads, 3, hd], rn [M, heads, 3] = 1 / n, 1 for v)."""
+    M = qkv.shape[0]
+    x, dx = qkv.to(dtype).view(M, heads, 3, hd), dqkv.to(dtype).view(M, heads, 3, hd)
+    n = x.norm(dim=-1).clamp_min(1e-12)
+    n[:, :, 2] = 1.0
+    f = 1.0 / n
+    f[:, :, 0] = f[:, :, 0] * scale.to(dtype).clamp(max=LN100).exp().view(1, heads)
+    c = (x * dx).sum(-1) / (n * n)
+    c[:, :, 2] = 0.0
+    return f[..., None] * x, f[..., None] * (dx - x * c[..., None]), 1.0 / n
+
+
+def qknorm_jvp_inputs(M, heads, hd, seed):
+    """fp32 (qkv, dqkv [M, 3 heads hd], scale [heads]): qkv = 0.7 randn, dqkv = randn; the last head's scale is ln 200 (clamped at
+    ln 100), head 0's ln 10; two all-zero primal vectors with their tangents left nonzero -- q of head 0 in the last row (tangent
+    tau dq 1e12) and k of the last head in row 0 (tangent dk 1e12)."""
+    g = torch.Generator().manual_seed(seed)
+    qkv, dqkv = 0.7 * torch.randn(M, 3 * heads * hd, generator=g), torch.randn(M, 3 * heads * hd, generator=g)
+    base = torch.log(torch.tensor([10.0, 3.0, 30.0, 60.0, 1.0, 99.0, 50.0, 20.0, 15.0, 5.0, 47.0, 200.0]))
+    scale = base[:heads].clone()
+    scale[heads - 1] = math.log(200.0)
+    v = qkv.view(M, heads, 3, hd)
+    v[M - 1, 0, 0] = 0.0
+    v[0, heads - 1, 1] = 0.0
+    return qkv, dqkv, scale
+
+
+def zero_vectors(M, heads):
+    """(row, head, part) of the all-zero vectors qknorm_jvp_inputs plants."""
+    return ((M - 1, 0, 0), (0, heads - 1, 1))
+
+
+def swiglu_tangent(h, dh, dtype=torch.float64):
+    """SwiGLU and its tangent on interleaved (gate_j, up_j) columns, in ``dtype`` (fp32: torch's own evaluation of the kernel's
+    formulas in the kernel's order): s = 1 / (1 + exp(-g)), out = g s u, d out = (s + g s (1 - s)) dg u + g s du.
+    Returns (out, d out, scale of out, scale of d out): the sums of the absolute terms an evaluation adds up --
+    |g s u| and (|s| + |g s (1 - s)|) |dg u| + |g s du| (the factor s + g s (1 - s) vanishes at g = -1.2784645)."""
+    h, dh = h.to(dtype), dh.to(dtype)
+    g, u, dg, du = h[:, 0::2], h[:, 1::2], dh[:, 0::2], dh[:, 1::2]
+    s = 1.0 / (1.0 + torch.exp(-g))
+    out = g * s * u
+    dout = (s + g * s * (1.0 - s)) * dg * u + g * s * du
+    return out, dout, out.abs(), (s.abs() + (g * s * (1.0 - s)).abs()) * (dg * u).abs() + (g * s * du).abs()
+
+
+def bf16_round_once(v64: torch.Tensor) -> torch.Tensor:
+    """fp64 -> the nearest bf16 value (ties to even) in ONE rounding, returned as fp64.  The usual route fp64 -> fp32 -> bf16 rounds
+    twice: with bf16 operands an exact result often lies within 2^-24 of a bf16 tie, the fp32 step lands on the tie, and the second
+    rounding then goes to the even neighbour instead of the nearer one."""
+    v = v64.double()
+    e = torch.frexp(v.abs().clamp_min(2.0 ** -126))[1] - 1                # floor(log2 |v|)
+    q = torch.ldexp(v, 7 - e)                                             # exact: |q| in [128, 256)
+    return torch.ldexp(torch.round(q), e - 7)                             # torch.round: halves to even
+
+
+def bf16_score_once(got: torch.Tensor, ref64: torch.Tensor):
+    """(worst |got - bf16(ref)| in bf16 ulps of bf16(ref), share of elements that differ from it), bf16(ref) rounded once."""
+    want = bf16_round_once(ref64)
+    e = torch.frexp(want.abs().clamp_min(2.0 ** -126))[1] - 1
+    ulp = torch.ldexp(torch.ones_like(want), e - 7)
+    return float(((got.double() - want).abs() / ulp).max()), float((got.double() != want).double().mean())
 
 
 def timestep_embed_tangent(t, dt, freqs, d: int, timestep_weight: float = 1.0, dtype=torch.float64):

@@ -118,6 +118,51 @@ def test_uniform_backward_is_the_column_mean(c):
     assert torch.equal(dv.bfloat16().float(), b["dv"]) and torch.equal(b["dv"], bf16_round(b["dv"]))
 
 
+@pytest.mark.parametrize("c", X.CASES, ids=IDS)
+def test_flat_tangent_has_one_answer(c):
+    """The flat family of the tangent entry: constant logit rows, W a bf16 value, every accumulation's sum of absolute terms below
+    2^24 units of its last place (so any order is exact, and so is the kernels' fp32 closing sequence), the closed form equal to
+    torch.func.jvp in fp64, every query row of an item with its own expected tangent row, and every one of dq, dk, dv visible in
+    every item."""
+    f, e = X.flat(c), X.flat_expected(c)
+    q, k, v, dq, dk, dv = (f[n] for n in ("q", "k", "v", "dq", "dk", "dv"))
+    for t in (q, k, v, dq, dk, dv):
+        assert torch.equal(t, bf16_round(t)) and float(t.abs().max()) > 0
+    assert bool(((q != 0).sum(-1) == 1).all()) and set(q.abs().amax(-1).unique().tolist()) == {1.0, 2.0, 4.0}      # rows s_i e_{a_i}
+    assert bool((k.gather(-1, X.flat(c)["A"].unsqueeze(-2).expand(*k.shape[:-1], X.FLAT_A)) == 1).all())
+    assert bool((dq.abs().sum(-1) == 4).all()) and bool((dk.abs().sum(-1) == 4).all())
+    # W = 1 x dS is an integer with |dS| <= 4 + 4 (four +-1 of dq against |k| <= 1, s_i <= 4 against one +-1 of dk): every integer up
+    # to 256 is a bf16 value, so bounding the maximum bounds them all
+    assert e["ds_max"] <= 8
+    assert e["budget"] < 2 ** 24
+    print(f"{c.name}: max |dS| {e['ds_max']:.0f}, largest sum of absolute terms {e['budget']:.3g} (2^24 = {2 ** 24})")
+    out, dout = e["out"], e["dout"]
+    assert float(out.abs().max()) * 256 <= 256                                                  # colsum(v) / 256 is a bf16 value
+    assert torch.equal(out.float().double(), out) and torch.equal(bf16_round(out.float()).double(), out)
+    assert torch.equal(dout.float().double(), dout)                                             # an fp32 value
+    # the kernels' closing sequence in fp32 on the exact sums reproduces it
+    for b in range(c.B):
+        qd, kd, vd, dqd, dkd, dvd = (f[n][b].double() for n in ("q", "k", "v", "dq", "dk", "dv"))
+        logits = qd @ kd.transpose(-2, -1)
+        assert torch.equal(logits, qd.sum(-1, keepdim=True).expand_as(logits))                  # every logit of row i is s_i
+        ds = dqd @ kd.transpose(-2, -1) + qd @ dkd.transpose(-2, -1)
+        u, tt, o = (ds @ vd).float(), dvd.sum(-2, keepdim=True).float(), vd.sum(-2, keepdim=True).float()
+        rl = torch.tensor(1.0 / 256.0)
+        rr = ds.sum(-1, keepdim=True).float() * rl
+        assert torch.equal(((u + tt - rr * o) * rl).double(), dout[b])
+        # fp64 forward-mode differentiation of softmax(q k^T) v
+        fn = lambda q_, k_, v_: (q_ @ k_.transpose(-2, -1)).softmax(-1) @ v_
+        ro, rd = torch.func.jvp(fn, (qd, kd, vd), (dqd, dkd, dvd))
+        assert float((ro - out[b]).abs().max()) < 1e-13 and float((rd - dout[b]).abs().max()) < 1e-12
+    # a misrouted row shows: the 256 expected tangent rows of an item are all different, also after the bf16 rounding
+    rows = bf16_round(dout.float()).reshape(-1, 256, c.hd)
+    assert all(len(r.unique(dim=0)) == 256 for r in rows)
+    # each product is pinned: without dq, dk or dv the expected tangent changes in every item
+    for name in ("dq", "dk", "dv"):
+        other = bf16_round(X.flat_expected(c, zero=(name,))["dout"].float()).reshape(-1, 256, c.hd)
+        assert bool((other != rows).flatten(1).any(1).all()), name
+
+
 def test_case_table_reaches_every_branch_and_entry():
     seen = set()
     for c in X.CASES:

@@ -8,6 +8,9 @@ selector are the residue of a cancellation and are held to the per-element bound
 the sample, window, head, row and column of the first wrong element.  tests/test_exact_attention_cpu.py proves on the oracle that
 each row's inputs have the answer demanded here.
 
+test_attention_tangent_flat_exact gives the tangent entry what the selector cannot (there dq = dk = 0 and P is one-hot, so dS, W, r
+and the correction -(r / l)(e V) never carry a nonzero value): the flat family, all six operands nonzero, in bf16 and in fp32.
+
 The last two tests localise the random-input comparisons of test_gpu_kernels.py and test_gpu_train.py: relative L2 per (sample,
 window, head) item against the fp64 formula, each item within 2 x its head's yardstick, which is the oracle's own bf16 emulation
 (the worse of its two softmax offsets; for the backward the plain bf16 restatement of exact_attention.py) measured the same way
@@ -217,6 +220,48 @@ def test_attention_backward_and_tangent_exact(dev, c, fam, entry):
                 pytest.fail(f"{c.name} {entry}: |d{name}| above the cancellation bound in {int(over.sum())} elements; first at sample {i[0]}, "
                             f"window {i[1]}, head {i[2]}, row {i[3]}, column {i[4]}: {float(got[tuple(i)]):.3e} > {float(bound[tuple(i)]):.3e}")
             print(f"{c.name} {entry}: max |d{name}| / bound = {float((got.abs() / bound).max()):.3e}")
+
+
+FLAT = [(c, f32) for c in X.CASES for f32 in (False, True)]
+
+
+@pytest.mark.parametrize("c,f32", FLAT, ids=[f"{c.name}-{'fp32' if f32 else 'bf16'}" for c, f32 in FLAT])
+def test_attention_tangent_flat_exact(dev, c, f32):
+    """swiftk_window_attention_jvp on the flat family (exact_attention.py): q, k, dq, dk, v, dv all nonzero, softmax flat per query
+    row.  out == colsum(v) / 256 and dout == (256 (dS V + 1 dV) - r (1 V)) / 65536 -- the value itself from the fp32 kernel
+    (attn_jvp_kernel<float, HD>: its first kernel-level test), its RNE rounding from the bf16 kernel -- every bit, over the remapped and
+    the plain block order, the three head widths, ragged item counts and wrap-around shifts of the table; head_dim 64 refuses.  The
+    operand rows are wider than 3 dim with NaN in the pad; pad columns and the extra row of both outputs keep their sentinels.
+    Measured on an MI355X: 0 differing elements [0] in all 22 running cases (4 .. 768 items), primal and tangent, bf16 and fp32; both
+    head_dim 64 cases refuse with their sentinels intact.  Passes on the parent commit: no defect found."""
+    F32, BF16 = codes()
+    rc_want = X.expected_rc(c, "jvp")
+    gh, gw = c.grid
+    W3, D, rows = 3 * c.dim, c.dim, c.B * c.n
+    ldq, ldo = W3 + 8, D + 4
+    dt = tdt(f32)
+
+    def operands():
+        both = torch.full((2, rows, ldq), float("nan"))
+        for i, t in enumerate(X.flat_qkv(c)):
+            both[i, :, :W3] = t.reshape(rows, W3)
+        return both.to(dt)
+
+    both = on_device(c, "flat", f"qkv{int(f32)}", operands, dev)
+    out, dout = X.sent((rows + 1, ldo), f32, dev), X.sent((rows + 1, ldo), f32, dev)
+    rc = L().swiftk_window_attention_jvp(both[0].data_ptr(), both[1].data_ptr(), ldq, out.data_ptr(), dout.data_ptr(), ldo, c.B, gh, gw, c.heads,
+                                         c.hd, c.shift[0], c.shift[1], F32 if f32 else BF16, st())
+    assert rc == rc_want, f"{c.name}: return code {rc}, the header's rules give {rc_want}"
+    blank = X.sent((rows + 1, ldo), f32)
+    if rc != 0:
+        check_bits(out, blank, c, "tangent kernel (refused), primal output", rows, D)
+        check_bits(dout, blank, c, "tangent kernel (refused), tangent output", rows, D)
+        return
+    e = X.flat_expected(c)
+    tag = f"flat, {'fp32' if f32 else 'bf16'} tangent kernel"
+    check_bits(out, want_buffer(c, X.to_tokens(c, e["out"].float()).reshape(c.B, c.n, D), f32, ldo), c, tag + ", primal output", rows, D)
+    check_bits(dout, want_buffer(c, X.to_tokens(c, e["dout"].float()).reshape(c.B, c.n, D), f32, ldo), c, tag + ", tangent output", rows, D)
+    print(f"{c.name} {tag}: 0 elements differ (bound 0), primal and tangent, {c.items} items")
 
 
 # ------------------------------------------------------------------------------------------------ random inputs, per item

@@ -5,6 +5,8 @@ torch.func.jvp / autograd of the oracle and shows that every term of the norm ta
 Tolerances: F32_TOL = 1e-5 relative L2 for fp32 results (one or two fp32 operations per element); a pair result's floor is its
 8-bit low part (6.5e-6), so 1e-5 for pair values and 1.5e-5 for the tangent increment; hostile rows are scored one by one against
 4 x the error of the fp32 restatement of the same arithmetic on the same row (computed here, printed beside the kernel's).
+swiftk_qknorm_jvp and swiftk_swiglu_jvp standing alone: per vector BF16_VEC_TOL = 2^-8 / F32_TOL, per element the bounds of
+test_swiglu_fwd_bwd_per_element (tests/test_gpu_backward_kernels.py); figures in the tests' docstrings.
 """
 import math
 
@@ -282,6 +284,179 @@ def test_modnorm_jvp_stream_scalar_equals_vector(dev, dtype):
     assert e < 2e-6
     for r in range(tr.HOSTILE_ROWS):  # (rows whose tangents are 1e3 times larger score on their own)
         assert rel_l2(xs[r].cpu(), xv[r].cpu()) < 2e-6 and rel_l2(dxs[r].cpu(), dxv[r].cpu()) < 2e-6, r
+
+
+# ------------------------------------------------------------------------------------------ QK-norm and SwiGLU tangents, alone
+
+def _dt_name(dt):
+    return "bf16" if dt == BF else "fp32"
+
+
+def _sent(shape, dt, dev):
+    """A buffer of ``dt`` holding the NaN pattern of exact_attention.sent in every element."""
+    import exact_attention as X
+    return X.sent(shape, dt == torch.float32, dev).view(dt)
+
+
+def _vec_rel_l2(got, ref):
+    """[..., hd] x 2 -> relative L2 per vector (fp64); a zero reference vector scores 0 when met exactly, inf otherwise."""
+    g, r = got.double(), ref.double()
+    num, den = (g - r).norm(dim=-1), r.norm(dim=-1)
+    return torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, torch.full_like(num, float("inf")), torch.zeros_like(num)))
+
+
+@pytest.mark.parametrize("with_rn", [True, False], ids=["rn", "rn-null"])
+@pytest.mark.parametrize("dt", [BF, torch.float32], ids=_dt_name)
+@pytest.mark.parametrize("M,heads,hd", tr.QKNORM_JVP_CASES)
+def test_qknorm_jvp_alone(dev, M, heads, hd, dt, with_rn):
+    """swiftk_qknorm_jvp in place on rows padded with the NaN pattern of exact_attention.sent (ld = width + 24, one extra row) against the fp64 closed form on the stored values
+    (tangent_reference.qknorm_tangent): every q / k vector, primal and tangent, within BF16_VEC_TOL = 2^-8 (bf16) / F32_TOL (fp32)
+    relative L2; the v third, the dv third and the pad keep their bits; rn = 1 / |x| to 1e-6 and exactly 1 for v, no entry left
+    unwritten, the row behind the last untouched.  18 and 3096 vectors: a ragged last block of 16; the last head's scale is ln 200
+    (clamped); two all-zero primal vectors keep a zero primal and get the finite tangent tau dx 1e12.
+    measured on MI355X (16 cases; bound in brackets): worst vector bf16 primal 2.0e-3 .. 2.4e-3, tangent 1.8e-3 .. 2.2e-3 [3.9e-3], medians
+    1.6e-3 .. 1.7e-3; fp32 primal 9.9e-8 .. 1.7e-7, tangent 9.5e-8 .. 1.9e-7 [1e-5], medians 3.1e-8 .. 4.9e-8; rn 5.8e-8 .. 1.3e-7 [1e-6].
+    Passes on the parent commit."""
+    from swift_amd import _lib, ops
+    L = _lib.lib()
+    width = 3 * heads * hd
+    ld = width + 24
+    q32, dq32, scale = tr.qknorm_jvp_inputs(M, heads, hd, 500 + M + hd)
+    qs, dqs = q32.to(dt).float(), dq32.to(dt).float()   # the values the kernel reads
+    buf, dbuf = _sent((M + 1, ld), dt, dev), _sent((M + 1, ld), dt, dev)
+    buf[:M, :width], dbuf[:M, :width] = qs.to(dev).to(dt), dqs.to(dev).to(dt)
+    before, dbefore = buf.clone(), dbuf.clone()
+    rn = _sent((M + 1, 3 * heads), torch.float32, dev)
+    rc = L.swiftk_qknorm_jvp(buf.data_ptr(), dbuf.data_ptr(), ld, scale.to(dev).data_ptr(), rn.data_ptr() if with_rn else None, M, heads, hd,
+                             ops.dtype_code(dt), s())
+    assert rc == 0
+    torch.cuda.synchronize()
+    ref, dref, rn_ref = tr.qknorm_tangent(qs, dqs, scale, heads, hd)
+    tol = 2.0 ** -8 if dt == BF else F32_TOL
+    tag = f"qknorm_jvp {_dt_name(dt)} M {M} heads {heads} head_dim {hd}{'' if with_rn else ' rn NULL'}"
+    for what, b_, b0, r_ in (("primal", buf, before, ref), ("tangent", dbuf, dbefore, dref)):
+        assert torch.equal(bits(b_[:, width:]), bits(b0[:, width:])) and torch.equal(bits(b_[M]), bits(b0[M])), f"{tag} {what}: pad or extra row written"
+        gv, bv = b_[:M, :width].reshape(M, heads, 3, hd), b0[:M, :width].reshape(M, heads, 3, hd)
+        assert torch.equal(bits(gv[:, :, 2]), bits(bv[:, :, 2])), f"{tag} {what}: the v third changed"
+        got = gv[:, :, :2].float().cpu()
+        assert torch.isfinite(got).all()
+        e = _vec_rel_l2(got, r_[:, :, :2])
+        w = int(e.flatten().argmax())
+        print(f"{tag} {what}: worst vector {float(e.max()):.2e} (row {w // (2 * heads)}, head {w // 2 % heads}, {'qk'[w % 2]}; bound {tol:.2e}), "
+              f"median {float(e.median()):.2e}")
+        assert float(e.max()) <= tol
+    for z in tr.zero_vectors(M, heads):
+        assert float(buf[z[0], (z[1] * 3 + z[2]) * hd:(z[1] * 3 + z[2] + 1) * hd].float().abs().max()) == 0.0   # the primal stays 0
+    if with_rn:
+        rg = rn.cpu()
+        assert torch.equal(bits(rg[M]), bits(_sent((3 * heads,), torch.float32, "cpu"))) and torch.isfinite(rg[:M]).all()
+        rg = rg[:M].view(M, heads, 3)
+        assert bool((rg[:, :, 2] == 1.0).all())
+        e = ((rg[:, :, :2].double() - rn_ref[:, :, :2]).abs() / rn_ref[:, :, :2]).max()
+        print(f"{tag}: rn worst relative error {float(e):.2e} (bound 1e-6)")
+        assert float(e) <= 1e-6
+
+
+@pytest.mark.parametrize("dt", [BF, torch.float32], ids=_dt_name)
+def test_qknorm_jvp_refusals(dev, dt):
+    """Head width 64, a row stride under the width and NULL pointers return the header's codes and write nothing."""
+    from swift_amd import _lib, ops
+    L = _lib.lib()
+    M, heads, hd = 3, 3, 88
+    width = 3 * heads * hd
+    buf, dbuf = (torch.full((M, width), 0.5, dtype=dt, device=dev) for _ in range(2))
+    scale, rn = torch.zeros(heads, device=dev), nan_like((M, 3 * heads), dev)
+    keep = [bits(t).clone() for t in (buf, dbuf, rn)]
+
+    def call(q=buf.data_ptr(), dq=dbuf.data_ptr(), ld=width, sc=scale.data_ptr(), hd_=hd):
+        return L.swiftk_qknorm_jvp(q, dq, ld, sc, rn.data_ptr(), M, heads, hd_, ops.dtype_code(dt), s())
+
+    assert call(hd_=64) == ESHAPE            # (3 heads of 64 need less room than the buffers have)
+    assert call(ld=width - 8) == ESHAPE
+    assert call(q=None) == EINVAL and call(dq=None) == EINVAL and call(sc=None) == EINVAL
+    torch.cuda.synchronize()
+    assert all(torch.equal(bits(t), k) for t, k in zip((buf, dbuf, rn), keep))
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert not torch.equal(bits(buf), keep[0]) and torch.isfinite(rn).all()
+
+
+@pytest.mark.parametrize("M,mlp", [(1, 8), (5, 37), (385, 2816)])
+@pytest.mark.parametrize("dt", [BF, torch.float32], ids=_dt_name)
+def test_swiglu_jvp_alone(dev, dt, M, mlp):
+    """swiftk_swiglu_jvp with both row strides larger than the widths and the NaN pattern of exact_attention.sent in every pad column, on backward_reference.swiglu_inputs
+    (the last row starts with the planted gates -100, -30, -1.2784645, 0, 30, 100) and a random tangent.  (385, 2816) is 1,084,160
+    items: the grid-stride loop's second trip with a ragged end.  Bounds as test_swiglu_fwd_bwd_per_element: bf16 within 1 bf16 ulp of
+    the rounded fp64 value and different from it on <= 1e-3 of the elements; fp32 within 8 x the error of torch's fp32 CPU evaluation
+    of the same formulas, both relative to the element's scale (tangent_reference.swiglu_tangent) + 2^-102.  Inputs and pads keep
+    their bits.
+    measured on MI355X (bound in brackets): bf16 against the fp64 value rounded once: tangent 0.00 ulp and 0 mismatches in all three
+    shapes, out (fp32 arithmetic) <= 1.00 ulp [1], mismatch share 1.2e-5 at (385, 2816) [1e-3]; against the fp64 value rounded through
+    fp32, as test_swiglu_fwd_bwd_per_element scores (asserted too): out 1.00 ulp, 8.3e-6; tangent 1.00 ulp, 1.0e-5 -- those 11
+    elements are the REFERENCE's second rounding: the exact value lies within 2^-24 of a bf16 tie (6.671874914 under 6.671875), its
+    fp32 rounding is the tie, and ties-to-even then picks the farther neighbour; the kernel, converting fp64 to bf16 directly,
+    returns the nearer one (tests/test_tangent_reference_cpu.py::test_bf16_round_once_rounds_once).  fp32 out 7.8e-8 .. 2.0e-7,
+    tangent 1.1e-7 .. 3.8e-7 of the element's scale, torch's fp32 evaluation on the CPU the same to two digits [8 x: 6.3e-7 ..
+    3.1e-6]; at the planted gate -30 out 6.7e-8 .. 1.3e-7, tangent 9.4e-9 .. 1.1e-7: the fp32 instantiation already took expf and a
+    true division and needed no cure.
+    [bf16-385-2816] fails on the parent commit: the tangent is a sum of two products, the two cancel to 2.5e-6 of their size at
+    element (7, 187) (below 2^-15 at twenty elements), and the fp32 evaluation stood 2.00 bf16 ulp from the rounded fp64 value there
+    (mismatch share 3.4e-5 through fp32) -- as does torch's own fp32 evaluation (2.00 ulp, 3.8e-5).  The bf16 instantiation now forms
+    its tangent in fp64, sigmoid included, and converts it to bf16 in one rounding (csrc/jvp_kernels.hip, swiglu_tangent): 0.00 ulp.
+    Its cost, printed by the (385, 2816) case: 141 us per call at (12288, 2816), 2.94 TB/s of the 12 bytes an element moves; the
+    parent's fp32 form was not timed on the same machine, so what the fp64 sigmoid adds is not known."""
+    import backward_reference as br
+    from swift_amd import _lib, ops
+    L = _lib.lib()
+    h32, _ = br.swiglu_inputs(M, mlp, 40 + M)
+    dh32 = rnd((M, 2 * mlp), 140 + M)
+    hv, dhv = h32.to(dt).float(), dh32.to(dt).float()   # the values the kernel reads
+    ldh, ldo = 2 * mlp + 16, mlp + 8
+    h, dh = _sent((M, ldh), dt, dev), _sent((M, ldh), dt, dev)
+    h[:, :2 * mlp], dh[:, :2 * mlp] = hv.to(dev).to(dt), dhv.to(dev).to(dt)
+    o, do = _sent((M + 1, ldo), dt, dev), _sent((M + 1, ldo), dt, dev)   # (outputs: the NaN pattern everywhere, one extra row)
+    h0, dh0, o0 = h.clone(), dh.clone(), o.clone()
+    assert L.swiftk_swiglu_jvp(h.data_ptr(), dh.data_ptr(), ldh, o.data_ptr(), do.data_ptr(), ldo, M, mlp, ops.dtype_code(dt), s()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(bits(h), bits(h0)) and torch.equal(bits(dh), bits(dh0))                               # inputs and their pads
+    assert torch.equal(bits(o[:, mlp:]), bits(o0[:, mlp:])) and torch.equal(bits(do[:, mlp:]), bits(o0[:, mlp:]))   # output pads
+    assert torch.equal(bits(o[M]), bits(o0[M])) and torch.equal(bits(do[M]), bits(o0[M]))                          # and the extra row
+    got = {"out": o[:M, :mlp].float().cpu(), "tangent": do[:M, :mlp].float().cpu()}
+    assert all(torch.isfinite(v).all() for v in got.values())
+    ro, rd, so, sd = tr.swiglu_tangent(hv, dhv)
+    ref, scale = {"out": ro, "tangent": rd}, {"out": so + 2.0 ** -102, "tangent": sd + 2.0 ** -102}
+    tag = f"swiglu_jvp {_dt_name(dt)} ({M}, {mlp})"
+    if dt == BF:
+        for k in got:
+            ulps, share = tr.bf16_score_once(got[k], ref[k])       # the fp64 value rounded once
+            ulps2, share2 = br.bf16_score(got[k], ref[k])          # ... and through fp32, as test_swiglu_fwd_bwd_per_element scores
+            print(f"{tag} {k}: worst {ulps:.2f} bf16 ulp from the rounded fp64 value (bound 1), mismatch share {share:.2e} (cap 1e-3); "
+                  f"from the fp64 value rounded through fp32 {ulps2:.2f} ulp, {share2:.2e}")
+            assert ulps <= 1.0 and share <= 1e-3, (k, ulps, share)
+            assert ulps2 <= 1.0 and share2 <= 1e-3, (k, ulps2, share2)
+        if M == 385:   # what the fp64 sigmoid costs the bf16 instantiation (printed, nothing asserted)
+            Mw = 12288
+            hw, dhw = (torch.randn(Mw, 2 * mlp, device=dev).to(dt) for _ in range(2))
+            ow, dow = (torch.empty(Mw, mlp, dtype=dt, device=dev) for _ in range(2))
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            for rep in range(3):
+                if rep == 1:
+                    ev[0].record()
+                assert L.swiftk_swiglu_jvp(hw.data_ptr(), dhw.data_ptr(), 2 * mlp, ow.data_ptr(), dow.data_ptr(), mlp, Mw, mlp, ops.dtype_code(dt), s()) == 0
+            ev[1].record()
+            torch.cuda.synchronize()
+            us = ev[0].elapsed_time(ev[1]) * 1e3 / 2
+            print(f"swiglu_jvp bf16 ({Mw}, {mlp}): {us:.0f} us per call, {12 * Mw * mlp / us / 1e6:.2f} TB/s of its 12 bytes per element")
+        return
+    yo, yd, _, _ = tr.swiglu_tangent(hv, dhv, torch.float32)
+    yard = {"out": yo, "tangent": yd}
+    for k in got:
+        ek = float(((got[k].double() - ref[k]).abs() / scale[k]).max())
+        ey = float(((yard[k].double() - ref[k]).abs() / scale[k]).max())
+        planted = ((got[k][M - 1, :min(6, mlp)].double() - ref[k][M - 1, :min(6, mlp)]).abs() / scale[k][M - 1, :min(6, mlp)]).tolist()
+        print(f"{tag} {k}: worst element error {ek:.2e} of its scale; torch fp32 on the CPU {ey:.2e}, bound 8 x = {8 * ey:.2e}; planted gates "
+              f"{[f'{v:.1e}' for v in planted]}")
+        assert ek <= 8 * ey, (k, ek, ey)
 
 
 # ------------------------------------------------------------------------------------------ SiLU, time embedding

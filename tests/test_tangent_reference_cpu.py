@@ -142,6 +142,69 @@ def test_silu_closed_forms():
     assert abs(float(tr.silu_grad(torch.tensor([90.0]))) - 1.0) < 1e-30 and abs(float(tr.silu_grad(torch.tensor([-90.0])))) < 1e-30
 
 
+@pytest.mark.parametrize("M,heads,hd", tr.QKNORM_JVP_CASES)
+def test_qknorm_tangent_equals_jvp_of_the_oracle_lines(M, heads, hd):
+    """oracle/swinv2.py, cosine_window_attention: q = q / |q|.clamp_min(1e-12) * exp(min(scale, ln 100)), k = k / |k|.clamp_min(1e-12),
+    differentiated by torch.func.jvp in fp64; the planted all-zero vectors keep a zero primal and get the finite tangent tau dx 1e12;
+    the builder's shapes leave a ragged last block of 16 vectors and one head above the clamp."""
+    qkv, dqkv, scale = tr.qknorm_jvp_inputs(M, heads, hd, 7)
+    assert (M * heads * 2) % 16 != 0 and float(scale[-1]) > tr.LN100 and float(scale[:-1].max()) < tr.LN100
+    x, dx = qkv.double().view(M, heads, 3, hd), dqkv.double().view(M, heads, 3, hd)
+    tau = torch.clamp(scale.double(), max=math.log(1.0 / 0.01)).exp().view(1, heads, 1)
+
+    def lines(t):
+        q, k, v = t[:, :, 0], t[:, :, 1], t[:, :, 2]
+        q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12) * tau
+        k = k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+        return torch.stack([q, k, v], dim=2)
+
+    zeros = tr.zero_vectors(M, heads)
+    live = torch.ones(M, heads, 3, dtype=torch.bool)
+    for z in zeros:
+        live[z] = False
+        assert float(x[z].abs().max()) == 0 and float(dx[z].abs().max()) > 0
+    ref, dref = torch.func.jvp(lines, (x,), (dx,))
+    got, dgot, rn = tr.qknorm_tangent(qkv, dqkv, scale, heads, hd)
+    assert rel_l2(got, ref) < 1e-14 and rel_l2(dgot[live], dref[live]) < 1e-13       # (autograd of norm() at 0 is a subgradient)
+    assert torch.equal(got[:, :, 2], x[:, :, 2]) and torch.equal(dgot[:, :, 2], dx[:, :, 2]) and bool((rn[:, :, 2] == 1).all())
+    assert rel_l2(rn[:, :, :2][live[:, :, :2]], 1.0 / x[:, :, :2].norm(dim=-1)[live[:, :, :2]]) < 1e-14
+    for z in zeros:   # the kernel's formula at |x| = 0: c = 0 / 1e-24 = 0, x-hat = 0, d x-hat = tau dx / 1e-12
+        t = float(tau[0, z[1], 0]) if z[2] == 0 else 1.0
+        assert float(got[z].abs().max()) == 0 and rel_l2(dgot[z], t * dx[z] * 1e12) < 1e-14 and float(rn[z]) == 1e12
+        assert bool(torch.isfinite(dgot[z].float().bfloat16()).all())
+    # the tangent is orthogonal to the direction: the term v (v . dv) / n^2 is pinned
+    assert float(((dgot[:, :, :2] * got[:, :, :2]).sum(-1)[live[:, :, :2]]).abs().max()) < 1e-10
+
+
+def test_swiglu_tangent_equals_jvp_of_the_oracle_line():
+    """oracle/swinv2.py: h = F.silu(h[..., :m]) * h[..., m:], on the interleaved columns, by torch.func.jvp in fp64 -- planted gates
+    included; the scales bound the terms, and torch's fp32 evaluation stays within a few fp32 epsilon of them."""
+    import backward_reference as br
+    h, _ = br.swiglu_inputs(5, 37, 45)
+    dh = rnd((5, 74), 46)
+    assert h[4, 0:12:2].tolist() == [pytest.approx(g) for g in br.PLANTED_GATES]
+    ref, dref = torch.func.jvp(lambda t: F.silu(t[:, 0::2]) * t[:, 1::2], (h.double(),), (dh.double(),))
+    out, dout, so, sd = tr.swiglu_tangent(h, dh)
+    assert float(((out - ref).abs() / (so + 1e-300)).max()) < 1e-14 and float(((dout - dref).abs() / (sd + 1e-300)).max()) < 1e-14
+    assert bool((out.abs() <= so).all()) and bool((dout.abs() <= sd * (1 + 1e-15)).all())
+    o32, d32, _, _ = tr.swiglu_tangent(h, dh, torch.float32)
+    assert o32.dtype == torch.float32
+    eo, ed = float(((o32.double() - out).abs() / (so + 2.0 ** -102)).max()), float(((d32.double() - dout).abs() / (sd + 2.0 ** -102)).max())
+    print(f"swiglu tangent, torch fp32 on the CPU: out {eo:.2e}, tangent {ed:.2e} of the element's scale")
+    assert eo < 2e-6 and ed < 2e-6
+
+
+def test_bf16_round_once_rounds_once():
+    """Equal to torch's fp32 -> bf16 rounding on fp32 values (powers of two, binade ends and ties included), and the nearer neighbour
+    where fp64 -> fp32 -> bf16 rounds twice: 6.671874913737452 (an element of test_swiglu_jvp_alone) is below the tie 6.671875."""
+    x = torch.cat([rnd((20000,), 9, 3.0), torch.tensor([1.0, 2.0, -0.5, 1.99609375, 1.998046875, 1.00390625, 1.01171875, 3e-5, -7e4])])
+    assert torch.equal(tr.bf16_round_once(x.double()), x.bfloat16().double())
+    v = torch.tensor([6.671874913737452, -0.001598358150361509], dtype=F64)
+    assert tr.bf16_round_once(v).tolist() == [6.65625, -0.00159454345703125]
+    assert v.float().bfloat16().double().tolist() == [6.6875, -0.0016021728515625]           # the twice-rounded route
+    assert tr.bf16_score_once(torch.tensor([6.65625]), v[:1]) == (0.0, 0.0)
+
+
 @pytest.mark.parametrize("B,d", [(3, 1056), (1, 2), (5, 97)])
 @pytest.mark.parametrize("w", [1.0, 1000.0])
 def test_timestep_embed_tangent(B, d, w):
