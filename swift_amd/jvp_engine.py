@@ -180,9 +180,15 @@ class SwinJvpEngine:
         return p.detach().float().contiguous()
 
     def jvp(self, srcs: Sequence[torch.Tensor], dsrc0: torch.Tensor, t: torch.Tensor, dt_: torch.Tensor,
-            aux: Optional[torch.Tensor], save_ctx: bool = False, want_logvar: bool = False):
+            aux: Optional[torch.Tensor], save_ctx: bool = False, want_logvar: bool = False, taps: Optional[dict] = None):
         """srcs: channel-concatenated network inputs (srcs[0] carries the tangent ``dsrc0``); t, dt_: [B].  Returns dF
         (after the first call of a signature: the captured sequence's own tensor, overwritten by the next call).
+
+        ``taps`` (tests, diagnostics): a dict to fill with fp32 COPIES of what the pass computes on its way -- ``emb`` / ``demb``,
+        ``lat`` / ``dlat``, ``mod`` / ``dmod`` ([B, 2 depth, 2, d]: slot, scale | shift) and the residual stream as [B, ntok, d]
+        after the patch embedding (``tok0`` / ``dtok0``), after each attention branch (``xmid{i}`` / ``dxmid{i}``) and after each
+        feed-forward branch (``x{i}`` / ``dx{i}``), the pair form decoded as ``ops.pair_value`` does.  Such a call runs eagerly
+        (no capture, no replay, the graph cache untouched); the launches of the pass itself are those of ``taps=None``.
 
         ``save_ctx``: the primal rows of the pass ARE a forward pass; keep them (per-layer buffers instead of one reused set)
         and return ``(dF, F, logvar, ctx)`` with ``ctx`` in the form ``SwinTrainEngine.backward`` takes -- the sCM loss
@@ -193,14 +199,15 @@ class SwinJvpEngine:
             ([aux.contiguous().float()] if aux is not None else [])
         n = len(srcs)
         key = ("jvp", tuple(tuple(s.shape) for s in srcs), aux is not None, bool(save_ctx), bool(want_logvar))
-        fn = lambda *a: self._jvp(list(a[:n]), a[n], a[n + 1], a[n + 2], a[n + 3] if aux is not None else None, save_ctx, want_logvar)
-        res = self.graphs.call(key, fn, ins)
+        fn = lambda *a: self._jvp(list(a[:n]), a[n], a[n + 1], a[n + 2], a[n + 3] if aux is not None else None, save_ctx, want_logvar,
+                                  taps)
+        res = fn(*ins) if taps is not None else self.graphs.call(key, fn, ins)
         if save_ctx:
             res[3]["graph_key"] = (key, max(1, self.graphs.generation.get(key, 0)))  # eager runs before the first capture count as generation 1
         return res
 
     def _jvp(self, srcs: Sequence[torch.Tensor], dsrc0: torch.Tensor, t: torch.Tensor, dt_: torch.Tensor,
-             aux: Optional[torch.Tensor], save: bool = False, want_logvar: bool = False):
+             aux: Optional[torch.Tensor], save: bool = False, want_logvar: bool = False, taps: Optional[dict] = None):
         m, T = self.m, self.dt
         tc = ops.dtype_code(T)
         dev = srcs[0].device
@@ -235,6 +242,9 @@ class SwinJvpEngine:
         mod = ops.linear_small(lat, self.mod_w, self.mod_b, 0)      # [B, depth * 2 * 2d]
         dmod = ops.linear_small(dlat, self.mod_w, None, 0)
         ldmod = mod.stride(0)
+        if taps is not None:
+            taps.update(emb=emb.clone(), demb=demb.clone(), lat=lat.clone(), dlat=dlat.clone(),
+                        mod=mod.view(B, -1, 2, d).clone(), dmod=dmod.view(B, -1, 2, d).clone())
         # ---- patch embedding: primal with bias + pos_embed, tangent without
         rest = sum(s.shape[1] for s in srcs[1:])
         ape = ops.patchify(srcs, [1.0] * len(srcs), m.patch_size, self.kpe, T)
@@ -286,6 +296,12 @@ class SwinJvpEngine:
                                        mod.data_ptr() + off, dmod.data_ptr() + off, ldmod, M, d, ntok, 1e-6, tc, _s()),
                   "swiftk_modnorm_jvp")
 
+        def tap(name, XT):  # read-only: fp32 copies of the stream's primal and tangent rows as they stand after a step
+            if taps is not None:
+                v = ops.pair_value(XT, XLO, d) if pair else X.clone()
+                taps[name], taps["d" + name] = v[:M].view(B, ntok, d), v[M:].view(B, ntok, d)
+
+        tap("tok0", XT_in)
         layers = []
         do_shift = any(m.shift_size)
         for i in range(len(self.L)):
@@ -309,6 +325,7 @@ class SwinJvpEngine:
             _gemm(ATT, W["wo"], Y1, k=inner)
             XT_mid = XT_in if shared else operand(self.kd, d)
             modnorm(2 * i, W["g1"], W["b1"], Y1, XT_mid, XT_in)
+            tap(f"xmid{i}", XT_mid)
             HM = shared["HM"] if shared else operand(self.kmlp, mlp)
             if fused:  # w1 with the gate and its tangent in the epilogue; the primal pre-activations are kept only for a backward pass
                 H = torch.empty(M, 2 * mlp, dtype=T, device=dev) if save else None
@@ -324,6 +341,7 @@ class SwinJvpEngine:
             _gemm(HM, W["w2"], Y2)
             XT_out = XT_mid if shared else operand(self.kd, d)
             modnorm(2 * i + 1, W["g2"], W["b2"], Y2, XT_out, XT_mid)
+            tap(f"x{i}", XT_out)
             if save:
                 layers.append(dict(xT_in=XT_in[:M], qkvh=QKV[:M], rn=rn, att=ATT[:M], y1=Y1[:M], xT_mid=XT_mid[:M], h=H[:M],
                                    hmid=HM[:M], y2=Y2[:M], shift=sh))

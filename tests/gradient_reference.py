@@ -24,6 +24,7 @@ from oracle.swinv2 import OracleNet
 FACTOR = 2.0          # bound = FACTOR x yardstick
 FLOOR = 0.1           # a slice whose truth is below FLOOR x the median slice norm is "under the floor"
 INPUT = "input:"      # key prefix of input gradients in a gradient dictionary
+FIELD = "field:"      # key prefix of a value (or tangent) of the network pass: out, tok0, xmid{i}, x{i}, mod, emb, lat
 # Where no bf16 rounding reaches a gradient (the logvar head: fp32 latent MLP, fp32 small-Linear backward) both emulations ARE
 # the fp32 oracle, the yardstick is that one summation order's accident (6e-7; exactly 0 for the logvar bias, a sum of B
 # numbers) and 2 x it would ask an atomically accumulated fp32 sum to be bit-exact.  Such a slicing is held to the bound the
@@ -119,6 +120,39 @@ def slicings(name, shape, cfg):
     if name.startswith(INPUT):                          # [B, C, H, W]: per (sample, channel)
         B, C = shape[:2]
         out["sample,channel"] = torch.arange(B * C).view(B, C, 1, 1)
+    elif name.startswith(FIELD):                        # a value of the network pass itself (tests/network_tangent_reference.py)
+        tap = name[len(FIELD):]
+        B = shape[0]
+        smp = torch.arange(B)
+        gh, gw = cfg.grid
+        wh, ww = cfg.window_size
+        nwx = gw // ww
+        nW = (gh // wh) * nwx
+
+        def windows(sh):                                # window of every token under roll(-sh) + partition (oracle window_token_index)
+            y, x = torch.arange(gh).view(-1, 1), torch.arange(gw).view(1, -1)
+            return ((y - sh[0]) % gh // wh) * nwx + (x - sh[1]) % gw // ww
+
+        if tap == "out":                                # [B, C, H, W]
+            C = shape[1]
+            p1, p2 = cfg.patch_size
+            px = lambda w: w.repeat_interleave(p1, 0).repeat_interleave(p2, 1).view(1, 1, gh * p1, gw * p2)
+            out["sample,channel"] = torch.arange(B * C).view(B, C, 1, 1)
+            out["sample,window"] = smp.view(B, 1, 1, 1) * nW + px(windows((0, 0)))
+            out["sample,shifted"] = smp.view(B, 1, 1, 1) * nW + px(windows(cfg.shift_size))
+        elif tap == "mod":                              # [B, 2 depth, 2, d]: slot, scale | shift
+            out["sample,slot,half"] = torch.arange(B * shape[1] * 2).view(B, shape[1], 2, 1)
+        elif len(shape) == 2:                           # [B, d]: emb, lat
+            out["sample"] = smp.view(B, 1)
+        else:                                           # the residual stream [B, gh gw, d] after tok0 / xmid{i} / x{i}
+            i = int(tap.lstrip("xmidtok"))
+            sh = cfg.shift_size if (tap != "tok0" and any(cfg.shift_size) and i % 2) else (0, 0)   # the layer that wrote it
+            n256, n352 = -(-B * gh * gw // 256), -(-d // 352)
+            rows = (smp.view(B, 1) * (gh * gw) + torch.arange(gh * gw).view(1, -1)).view(B, -1, 1)
+            out["sample,window"] = smp.view(B, 1, 1) * nW + windows(sh).reshape(1, -1, 1)
+            out["sample,headblk"] = smp.view(B, 1, 1) * -(-d // hd) + _blocks(d, hd).view(1, 1, -1)
+            out["tile256x352"] = rows // 256 * n352 + _blocks(d, 352).view(1, 1, -1)   # the GEMM's output tile over [B gh gw, d]
+            assert int(out["tile256x352"].max()) + 1 == n256 * n352
     elif name.endswith("to_qkv.weight"):                # rows [head][q | k | v][hd] (oracle/swinv2.py cosine_window_attention)
         r = torch.arange(shape[0])
         out["third,head"] = col((r // hd) % 3 * heads + r // (3 * hd))
