@@ -696,6 +696,30 @@ int swiftk_ensemble_summary(const float* pred, const int* q_lo, const double* q_
  * are not restricted. */
 int swiftk_ensemble_maps(const float* pred, const float* y, double* acc, int n, int N, int V, int H, int W, int accumulate,
                          void* stream);
+/* Means over lead-time windows: the week-1 / week-2 / weeks 3-4 fields that `generate --lead-windows` scores (past about day 10 a
+ * forecast is verified as the time mean over a window of leads, not step by step).  The reference has no counterpart: its users
+ * dump every member and reduce the store offline.
+ * x [n, M] fp32 contiguous on the device: n lead steps of M values each (one IC: M = members V H W; its verifying fields: M =
+ * V H W); out [nw, M] fp32 on the device.  first [nw] and count [nw] are HOST arrays of ints, read before the call returns and
+ * handed to the kernel by value: no device table, no copy, no memset.  Window w covers the lead rows first[w] .. first[w] +
+ * count[w] - 1; windows may overlap, nest, repeat or leave rows out, in any order.
+ * Per column j and window w, every operation one correctly rounded fp64 operation, never fused:
+ *   s = (double) x[first, j]; for the window's further rows r in ascending order s = s + (double) x[r, j];
+ *   out[w, j] = (float)(s / (double) count): one division, one round-to-nearest cast.
+ * The sum starts from the window's first element, not from +0: a window of one step returns its input bit for bit, -0, subnormals
+ * and infinities included (a NaN stays a NaN; its payload is not promised).  The bits of out[w, j] depend on that column's values
+ * in the window and on count only -- not on M, n, nw, the window's position, the other windows or the rank.  NaN and infinities
+ * propagate as IEEE has them, into the windows that hold them and no others; an element of x outside every window is never read.
+ * fp64 because fp32 fails here: 28 steps at 280 K under 1e-2 K of variation lose the mean's last bits on most columns.
+ * A thread owns 4 columns -- as one 16-byte access where x, out and M allow it (both on 16-byte boundaries, M a multiple of 4),
+ * as 4 coalesced dwords otherwise, the same bits either way -- and walks the lead rows spanned by the windows once, 8 rows' loads
+ * in flight, with one fp64 running sum per window and column in registers: every element of x that lies in any window is read
+ * once per call however the windows overlap.  All index arithmetic is 64-bit (n M may exceed 2^31).  No atomics, no scratch, and
+ * out is written completely by every call: the caller clears nothing.
+ * Refused before any launch: a null pointer, a non-positive n, nw or M (SWIFTK_EINVAL); nw > 8, a window with first < 0,
+ * count < 1 or first + count > n (SWIFTK_ESHAPE); x or out off a 4-byte boundary (SWIFTK_EALIGN). */
+int swiftk_lead_window_mean(const float* x, float* out, const int* first, const int* count, int n, int nw, int64_t M,
+                            void* stream);
 /* Ensemble evaluation sums (eval/metrics.py:39-134), pred [B, N, V, H, W], y [B, V, H, W], out [B, V, 4] (zero-filled by
  * the caller): per (sample, variable) the latitude-weighted grid sums of (ens-mean - y)^2, sum_n |x_n - y|,
  * sum_{n,n'} |x_n - x_n'| and the unbiased member variance; 2 <= N <= 64.  RMSE / CRPS / spread-skill follow on the host.

@@ -135,6 +135,7 @@ _SIGS = {
     "swiftk_event_table": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_ensemble_summary": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_ensemble_maps": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
+    "swiftk_lead_window_mean": ([_p, _p, _p, _p, _i, _i, _l, _p], _i),
     "swiftk_scm_target": ([_p, _p, _p, _p, _p, _f, _f, _p, _p, _i, _l, _p], _i),
     "swiftk_gemm_qkv_tiled": ([_p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "swiftk_qkv_attention_fused": ([_p, _l, _p, _l, _p, _p, _l, _l, _i, _i, _i, _i, _i, _i, _i, _p], _i),

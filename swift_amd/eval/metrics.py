@@ -300,6 +300,91 @@ def ensemble_maps(pred: torch.Tensor, y: torch.Tensor, acc: torch.Tensor = None)
     return acc
 
 
+MAX_LEAD_WINDOWS, LEAD_WINDOWS_PER_CALL = 32, 8  # what a job takes; what swiftk_lead_window_mean takes in one call
+WINDOWS_FILE = "evaluation_windows.json"
+
+
+def parse_lead_windows(specs, steps: int, interval: int):
+    """The lead-time windows of ``generate --lead-windows SPEC ...`` -> (names [nw], first int32 [nw], count int32 [nw]), the host
+    tables of ``lead_window_mean`` over the leads 1 .. ``steps`` of a rollout (row 0 is the lead ``interval`` hours).  A spec is
+    ``A-B`` or ``A-Bh``: the lead hours A to B, both ends included (``6-168`` is week 1 of a 6-hourly job); its name is
+    ``<A>-<B>h``.  ``ValueError`` naming the spec -- pure host work, before any rank is started or the GPU is touched -- for a
+    malformed spec, A below ``interval`` (lead 0 is not a forecast), A > B, A or B not a multiple of ``interval``, B beyond
+    ``steps * interval``, a window given twice, more than 32 windows, none at all."""
+    import re
+    steps, interval = int(steps), int(interval)
+    specs = [str(s) for s in (specs or [])]
+    if not specs:
+        raise ValueError("lead windows: no windows given (--lead-windows <A>-<B> ..., lead hours, both ends included)")
+    if len(specs) > MAX_LEAD_WINDOWS:
+        raise ValueError(f"lead windows: at most {MAX_LEAD_WINDOWS} windows, got {len(specs)}: '{specs[MAX_LEAD_WINDOWS]}' is one too many")
+    names, first, count = [], [], []
+    for spec in specs:
+        m = re.fullmatch(r"(\d+)-(\d+)h?", spec)
+        if not m:
+            raise ValueError(f"lead windows: '{spec}' is not <A>-<B> or <A>-<B>h (lead hours, both ends included)")
+        a, b = int(m.group(1)), int(m.group(2))
+        if a < interval:
+            raise ValueError(f"lead windows: '{spec}' starts at {a} h, before the first forecast lead {interval} h (lead 0 is not a forecast)")
+        if a > b:
+            raise ValueError(f"lead windows: '{spec}' ends before it starts")
+        if a % interval or b % interval:
+            raise ValueError(f"lead windows: '{spec}' does not lie on the {interval}-hourly leads of this job")
+        if b > steps * interval:
+            raise ValueError(f"lead windows: '{spec}' ends after the last lead of this job, {steps * interval} h ({steps} steps of {interval} h)")
+        name = f"{a}-{b}h"
+        if name in names:
+            raise ValueError(f"lead windows: '{spec}' is given twice")
+        names.append(name), first.append(a // interval - 1), count.append((b - a) // interval + 1)
+    return names, np.asarray(first, dtype=np.int32), np.asarray(count, dtype=np.int32)
+
+
+def _window_tables(what: str, first, count, n: int):
+    first, count = np.asarray(first), np.asarray(count)
+    if not (first.ndim == 1 and first.size > 0 and first.shape == count.shape and first.dtype.kind in "iu" and count.dtype.kind in "iu"):
+        raise ValueError(f"{what}: first [nw] and count [nw] integers expected, got {first.dtype} {first.shape} and {count.dtype} {count.shape}")
+    first, count = first.astype(np.int64), count.astype(np.int64)
+    if first.min() < 0 or count.min() < 1 or (first + count).max() > n:
+        raise ValueError(f"{what}: windows first {first.tolist()} count {count.tolist()} do not lie inside the {n} lead rows")
+    return first, count
+
+
+def lead_window_mean(x: torch.Tensor, first, count) -> torch.Tensor:
+    """Means over windows of the leading (lead-time) axis (definition: include/swiftk.h, ``swiftk_lead_window_mean``: an fp64
+    running sum in lead order from the window's first element, one division, one cast).  x [n, ...] contiguous fp32 on the device,
+    ``first`` / ``count`` [nw] host integers (``parse_lead_windows``): window w the rows first[w] .. first[w] + count[w] - 1 ->
+    [nw, ...] fp32 on the device, written completely.  More than 8 windows go out as several launches of at most 8."""
+    import ctypes
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.ndim >= 1 and x.dtype == torch.float32 and x.numel() > 0
+            and x.is_contiguous()):
+        raise ValueError(f"lead_window_mean: a contiguous fp32 device tensor [n, ...] expected, got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', None)}")
+    n = x.shape[0]
+    M = x.numel() // n
+    first, count = _window_tables("lead_window_mean", first, count, n)
+    nw = first.size
+    out = torch.empty((nw,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)  # written completely by the calls
+    for w0 in range(0, nw, LEAD_WINDOWS_PER_CALL):
+        k = min(LEAD_WINDOWS_PER_CALL, nw - w0)
+        f, c = (ctypes.c_int * k)(*first[w0:w0 + k].tolist()), (ctypes.c_int * k)(*count[w0:w0 + k].tolist())
+        check(lib().swiftk_lead_window_mean(x.data_ptr(), out.data_ptr() + w0 * M * 4, f, c, n, k, M,
+                                            torch.cuda.current_stream().cuda_stream), "swiftk_lead_window_mean")
+    return out
+
+
+def window_scores(sums, names, variables, members: int, hw) -> Dict[str, float]:
+    """Per-IC ``ensemble_sums`` rows of window-mean fields, sums [n_ic, nw, nv, 4] fp64 -> the flat ``evaluation_windows.json``
+    dict ``rmse_`` / ``crps_`` / ``ssr_<var>_<A>-<B>h``: ``scores_from_sums`` per window, the conventions of
+    evaluation_metrics.json (the IC-mean of the per-IC RMSE, and so on)."""
+    sums = sums if isinstance(sums, torch.Tensor) else torch.from_numpy(np.asarray(sums, dtype=np.float64))
+    res = {}
+    for w, name in enumerate(names):
+        rmse, crps, ssr = scores_from_sums(sums[:, w], members, hw)    # [n_ic, nv, 4] -> [nv] each
+        for i, v in enumerate(variables):
+            res[f"rmse_{v}_{name}"], res[f"crps_{v}_{name}"], res[f"ssr_{v}_{name}"] = float(rmse[i]), float(crps[i]), float(ssr[i])
+    return res
+
+
 def region_means(maps: np.ndarray, lat) -> Dict[str, np.ndarray]:
     """Latitude-weighted regional means of maps [..., H, W] (fp64) -> {region: [...]}: weights cos(lat), normalised over the
     region's rows.  Regions (the WeatherBench2 bands): ``global``, ``tropics`` (|lat| <= 20), ``n_extratropics`` (lat >= 20),
@@ -388,7 +473,7 @@ def _cf_lead_hours(root: str, name: str = "prediction_timedelta") -> list:
     return [int(x) for x in (v.astype(np.float64) * _unit_ns(unit) / _UNIT_NS["hours"]).round().astype(np.int64)]
 
 
-def evaluate_stores(truth: str, pred: str, device=None, sums_fn=None, log=print) -> Dict[str, float]:
+def evaluate_stores(truth: str, pred: str, device=None, sums_fn=None, log=print, windows=None, mean_fn=None):
     """The reference's ``python -m swift.eval.metrics --truth T.zarr --pred P.zarr`` (eval/metrics.py:157-222): for every lead time of
     the forecast store and every variable (pressure-level variables level by level), latitude-weighted ensemble-mean RMSE, CRPS
     and spread/skill ratio against the truth store's fields at ``init time + lead`` -- keys ``<metric>_<var>[_<level>]_<lead>h``.
@@ -398,11 +483,20 @@ def evaluate_stores(truth: str, pred: str, device=None, sums_fn=None, log=print)
     in the layout ``generate`` writes), the [lead, member, level, H, W] block of that IC goes to the device once and ONE
     ``swiftk_ensemble_sums`` launch per variable and IC yields the sums of every lead and level; the per-IC sums are combined at
     the end exactly as the reference's batch means are.  ``sums_fn(pred[T, N, V, H, W], y[T, V, H, W], lat) -> [T, V, 4]``
-    replaces the device kernel in the host-logic tests."""
+    replaces the device kernel in the host-logic tests.
+
+    ``windows`` (the specs of ``--lead-windows``, checked by ``parse_lead_windows`` against the store's own lead times) adds the
+    scores of the lead-time-mean fields: per IC and variable the block and its verifying fields are averaged over every window
+    (``swiftk_lead_window_mean``) and the means go through the same sums -- and the call returns (flat, flat_windows), the second
+    dict with the keys ``<metric>_<var>[_<level>]_<A>-<B>h`` of evaluation_windows.json.  ``mean_fn(x[T, ...], first, count) ->
+    [nw, ...]`` replaces that kernel in the host-logic tests."""
     from ..utils import zarrlite
-    if sums_fn is None:
+    if sums_fn is None or (windows and mean_fn is None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if sums_fn is None:
         sums_fn = lambda p, y, lat: ensemble_sums(torch.from_numpy(p).to(dev), torch.from_numpy(y).to(dev), lat).double().cpu().numpy()
+    if windows and mean_fn is None:
+        mean_fn = lambda x, first, count: lead_window_mean(torch.from_numpy(x).to(dev), first, count).cpu().numpy()
     lat = zarrlite.read_array(truth, "latitude").astype(np.float64)
     init_times, truth_times = _cf_times(pred), _cf_times(truth)
     where = {int(t): i for i, t in enumerate(truth_times.astype(np.int64))}
@@ -415,7 +509,14 @@ def evaluate_stores(truth: str, pred: str, device=None, sums_fn=None, log=print)
     offs = [h // dt_truth for h in leads]
     if init_idx.max() + max(offs) >= len(truth_times):
         raise ValueError("the truth store ends before the forecasts' last verification time")
+    if windows:
+        lead0 = int(leads[0] == 0)  # (the stores of generate begin with the initial condition, lead 0: not a forecast)
+        fl = leads[lead0:]
+        if not fl or fl[0] <= 0 or fl != [(j + 1) * fl[0] for j in range(len(fl))]:
+            raise ValueError(f"lead windows: the forecast store's lead times {leads} h are not the steps 1 .. n of one interval")
+        wnames, wfirst, wcount = parse_lead_windows(windows, len(fl), fl[0])
     out: Dict[str, float] = {}
+    wout: Dict[str, float] = {}
     for var in [v for v in zarrlite.list_arrays(pred) if v not in _COORDS]:
         shape, _dt, _dims = zarrlite.array_info(pred, var)
         levelled = var in PRESSURE_LEVEL_VARS
@@ -425,19 +526,26 @@ def evaluate_stores(truth: str, pred: str, device=None, sums_fn=None, log=print)
         L = shape[3] if levelled else 1
         names = [f"{var}_{DEFAULT_PRESSURE_LEVELS[i]}" for i in range(L)] if levelled else [var]  # (by position, as the reference)
         sums = np.zeros((B, T, L, 4))
+        wsums = np.zeros((B, len(wnames), L, 4)) if windows else None
         for b in range(B):
             p = np.asarray(zarrlite.read_region(pred, var, (b,)), dtype=np.float32)                 # [N, T, (L,) H, W]
             y = np.stack([np.asarray(zarrlite.read_region(truth, var, (int(init_idx[b] + o),)), dtype=np.float32) for o in offs], 0)
             if not levelled:
                 p, y = p[:, :, None], y[:, None]
-            sums[b] = sums_fn(np.ascontiguousarray(p.transpose(1, 0, 2, 3, 4)), np.ascontiguousarray(y), lat)
+            p, y = np.ascontiguousarray(p.transpose(1, 0, 2, 3, 4)), np.ascontiguousarray(y)
+            sums[b] = sums_fn(p, y, lat)
+            if windows:
+                wsums[b] = sums_fn(mean_fn(p[lead0:], wfirst, wcount), mean_fn(y[lead0:], wfirst, wcount), lat)
         hw = float(shape[-1] * shape[-2])
         for j, h in enumerate(leads):   # the batch statistics of eval/metrics.py:39-134 from the per-IC sums (as generate --metrics)
             rmse, crps, ssr = scores_from_sums(torch.from_numpy(sums[:, j]), N, hw)
             for i, nm in enumerate(names):
                 out[f"crps_{nm}_{h}h"], out[f"rmse_{nm}_{h}h"], out[f"ssr_{nm}_{h}h"] = float(crps[i]), float(rmse[i]), float(ssr[i])
-        log(f"{var}: {B} initial conditions x {N} members x {T} lead times" + (f" x {L} levels" if levelled else ""))
-    return out
+        if windows:
+            wout.update(window_scores(wsums, wnames, names, N, hw))
+        log(f"{var}: {B} initial conditions x {N} members x {T} lead times" + (f" x {L} levels" if levelled else "")
+            + (f", {len(wnames)} lead windows" if windows else ""))
+    return (out, wout) if windows else out
 
 
 def structure(flat: Dict[str, float]) -> Dict[str, dict]:
@@ -458,10 +566,20 @@ def main(argv=None):
     ap.add_argument("--pred", required=True, help="Path to prediction (zarr store of swift.generate; or its output-*.npy)")
     ap.add_argument("--lat", default=None, help="npy mode: latitudes (default: linspace(-90, 90, H))")
     ap.add_argument("--interval", type=int, default=6, help="npy mode: hours per step")
+    ap.add_argument("--lead-windows", type=str, nargs="+", default=None, metavar="SPEC", help="zarr mode: also score the means over "
+                    "the lead hours A to B (both included) of each SPEC A-B, as generate --lead-windows -> evaluation_windows.json")
     a = ap.parse_args(argv)
+    if a.lead_windows and a.pred.rstrip("/").endswith(".npy"):
+        raise SystemExit("--lead-windows scores a zarr forecast store (--pred P.zarr --truth T.zarr); the npy mode does not take it")
     if not a.pred.rstrip("/").endswith(".npy"):
         t0 = time.time()
-        flat = evaluate_stores(a.truth, a.pred)
+        flat = evaluate_stores(a.truth, a.pred, windows=a.lead_windows)
+        if a.lead_windows:
+            flat, wflat = flat
+            wpath = os.path.join(os.path.dirname(os.path.abspath(a.pred.rstrip("/"))), WINDOWS_FILE)
+            with open(wpath, "w") as f:
+                json.dump(wflat, f, indent=1)
+            print(f"wrote {wpath} ({len(wflat)} metrics of {len(a.lead_windows)} lead windows)")
         path = os.path.join(os.path.dirname(os.path.abspath(a.pred.rstrip("/"))), "evaluation_metrics.json")
         with open(path, "w") as f:
             json.dump({"metadata": {"prediction_file": os.path.abspath(a.pred), "truth_file": os.path.abspath(a.truth),

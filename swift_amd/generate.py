@@ -41,7 +41,12 @@ per-grid-point threshold field from the file, NaN where a pixel is left out -- a
 table of the number of members in the event against the outcome, ``swiftk_event_table`` in exact integers and fp64 on the device,
 and from it the reliability diagram, the Brier score with its reliability / resolution / uncertainty decomposition, the fair
 Brier score and the skill score against climatology: the probability of an event, which lives in the tails where a score of the
-whole distribution looks least) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
+whole distribution looks least), ``--lead-windows SPEC ...`` (implies ``--metrics``; adds ``evaluation_windows.json``: for every
+window of lead hours ``A-B``, both ends included -- ``6-168 174-336`` are weeks 1 and 2 of a 6-hourly job -- the RMSE, CRPS and
+spread/skill ratio of the lead-time-MEAN fields, members and verifying fields averaged over the window by
+``swiftk_lead_window_mean`` in fp64 on the device and scored by ``swiftk_ensemble_sums`` like an instantaneous field: what is
+verified past day 10, where a forecast can have lost its skill at every single step and still have a useful weekly mean, and
+where a drifting model shows first) and ``--gpus N`` (start the N ranks from a bare ``python -m`` call).
 """
 from __future__ import annotations
 
@@ -58,7 +63,8 @@ import torch.distributed as tdist
 
 from . import dist
 from .config import Cfg, instantiate, load_saved
-from .eval.metrics import BRIER_SCORES, MAP_STATISTICS, brier_scores, parse_events, quantile_table, region_means, scores_from_sums
+from .eval.metrics import (BRIER_SCORES, MAP_STATISTICS, WINDOWS_FILE, brier_scores, parse_events, parse_lead_windows, quantile_table,
+                           region_means, scores_from_sums, window_scores)
 from .rollout import RolloutEngine, unit_seed
 from .utils import zarrlite
 
@@ -106,6 +112,9 @@ parser.add_argument("--events", type=str, nargs="+", default=None, metavar="SPEC
                     "score -> evaluation_brier.json")
 parser.add_argument("--events-file", type=str, default=None, metavar="FILE.npz", help="implies --metrics; further events: keys "
                     "<variable>:<gt|lt>:<label>, values a scalar or an [H, W] threshold field, NaN where a pixel is left out")
+parser.add_argument("--lead-windows", type=str, nargs="+", default=None, metavar="SPEC", help="implies --metrics; lead-time windows "
+                    "A-B (lead hours, both ends included: 6-168 174-336 are weeks 1 and 2): RMSE, CRPS and spread/skill of the "
+                    "fields averaged over each window -> evaluation_windows.json")
 parser.add_argument("--quantiles", type=float, nargs="+", default=[0.1, 0.5, 0.9], help="quantiles of --summary, each in [0, 1], "
                     "at most 16 (default: 0.1 0.5 0.9)")
 
@@ -437,6 +446,36 @@ def collect_events(local, n_ic, members, names, variables, interval, odir):
     return arrays
 
 
+def check_windows_args(args):
+    """``--lead-windows`` checked on the host (``ValueError``), before any rank is started or the GPU is touched: 2 .. 64 members,
+    and ``parse_lead_windows`` against the job's ``--steps`` and ``--interval``."""
+    if getattr(args, "lead_windows", None):
+        if not 2 <= args.members <= 64:
+            raise ValueError(f"--lead-windows takes the CRPS and the spread over 2 .. 64 members, got --members {args.members}")
+        parse_lead_windows(args.lead_windows, args.steps, args.interval)
+
+
+def collect_windows(sums, n_ic, names, nv, members, dataset, device, odir):
+    """Output collection of ``--lead-windows``, as ``collect_metrics``: every rank contributes the ensemble sums of the window-mean
+    fields of its ICs ([n_ic, nw, nv, 4], zeros elsewhere: an IC's slot comes from one rank and is added to zeros, so the file
+    does not depend on ``--gpus`` or ``--batch``), one all-gather, rank 0 applies ``scores_from_sums`` per window and writes
+    ``evaluation_windows.json``: ``rmse_`` / ``crps_`` / ``ssr_<var>_<A>-<B>h``, the conventions of evaluation_metrics.json."""
+    local = torch.zeros(n_ic, len(names), nv, 4, dtype=torch.float64)
+    for ic, v in sums.items():
+        local[ic] = v
+    total = torch.stack(dist.all_gather_parts(local, device), 0).sum(0).cpu() if dist.collectives_active() else local
+    if dist.get_rank() != 0:
+        return None
+    H, W = dataset.img_resolution
+    res = window_scores(total, names, dataset.variables, members, H * W)
+    path = os.path.join(odir, WINDOWS_FILE)
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    dist.log0(f"lead-window scores (--lead-windows) of {n_ic} ICs x {members} members, windows {', '.join(names)}, gathered from "
+              f"{dist.get_world_size()} rank(s): {path}")
+    return res
+
+
 def load_cfg(args) -> Cfg:
     """The run's saved composed config (generate.py:161), or the synthetic one when ``--synthetic`` names no run directory."""
     if args.synthetic and not os.path.exists(os.path.join(args.input, ".hydra", "config.yaml")):
@@ -483,6 +522,7 @@ def main(args):
     check_maps_args(args)
     cfg = load_cfg(args)
     check_events_args(args, cfg)
+    check_windows_args(args)
     solver, solver_kwargs = solver_setup(cfg, args.solver, args.num_steps, args.interval)
     dist.setup_torch(backend=cfg.system.torch.backend)
     np.random.seed(cfg.seed % (1 << 31))
@@ -497,7 +537,7 @@ def main(args):
     net, ckpt_basename = build_net(cfg, dataset, args, device)
 
     from .generating.products import MetricSums, product_types
-    args.metrics = MetricSums in product_types(args)  # (--spectra, --rank-hist, --maps and --events imply the metric sums)
+    args.metrics = MetricSums in product_types(args)  # (--spectra, --rank-hist, --maps, --events and --lead-windows imply the metric sums)
     if args.dump is None:  # (see --dump: the raw store is the one-rank default, metrics only the multi-rank one)
         args.dump = "zarr" if dist.get_world_size() == 1 else "none"
         if args.dump == "none":
@@ -553,5 +593,6 @@ if __name__ == "__main__":
     check_summary_args(_args)
     check_maps_args(_args)
     check_events_args(_args)
+    check_windows_args(_args)
     dist.maybe_launch_ranks(_args.gpus, "swift_amd.generate")  # before anything touches the GPU; returns in the ranks
     main(_args)

@@ -189,6 +189,29 @@ class Events(Product):
                                 [str(self.variables[v]) for v in self.ev_var], self.interval, self.odir)
 
 
+class LeadWindows(Product):
+    """--lead-windows: per IC the members and the verifying fields averaged over every window of leads (swiftk_lead_window_mean)
+    and the swiftk_ensemble_sums of those means, [nw, nv, 4] -- a window scored like one more lead step.  The windows are parsed
+    on the host when the product is made."""
+
+    def __init__(self, *job, specs):
+        super().__init__(*job)
+        self.names, self.first, self.count = metrics.parse_lead_windows(specs, self.steps, self.interval)
+        self.logged = False
+
+    def add_ic(self, ic, traj, pred, y):
+        pm = metrics.lead_window_mean(pred, self.first, self.count)                 # [nw, members, nv, H, W]
+        ym = metrics.lead_window_mean(y.contiguous(), self.first, self.count)       # [nw, nv, H, W]
+        self.sums[ic] = metrics.ensemble_sums(pm, ym, self.lat).double().cpu()
+        if not self.logged:
+            self.logged = True
+            dist.log0(f"--lead-windows: {pm.numel() * 4 / 1e9:.2f} GB of fp32 window means {list(pm.shape)} per IC, on the device "
+                      "until the IC is scored")
+
+    def finish(self):
+        generate.collect_windows(self.sums, self.n_ic, self.names, self.nv, self.members, self.dataset, self.device, self.odir)
+
+
 class Summary(Product):
     """--summary: swiftk_ensemble_summary of the IC's members at every lead step, lead 0 included.  The [steps + 1, 2 + Q, nv, H,
     W] result stays on the device until the summary thread has taken it -- through one pinned buffer on a stream of its own -- and
@@ -232,10 +255,11 @@ class Summary(Product):
 
 
 def product_types(args) -> list:
-    """The product classes of a command line, in feeding order: --spectra, --rank-hist, --maps and --events / --events-file imply
-    the metric sums."""
+    """The product classes of a command line, in feeding order: --spectra, --rank-hist, --maps, --events / --events-file and
+    --lead-windows imply the metric sums."""
     implying = [c for c, flag in ((Spectra, "spectra"), (RankHistogram, "rank_hist"), (Maps, "maps")) if getattr(args, flag, False)]
     implying += [Events] if getattr(args, "events", None) or getattr(args, "events_file", None) else []
+    implying += [LeadWindows] if getattr(args, "lead_windows", None) else []
     truth = [MetricSums] + implying if implying or getattr(args, "metrics", False) else []
     return truth + ([Summary] if getattr(args, "summary", False) else [])
 
@@ -243,7 +267,8 @@ def product_types(args) -> list:
 def products_from_args(args, dataset, members, steps, ofile, device, n_ic=None, interval=6, loaders=None) -> list:
     job = (dataset, members, steps, n_ic, interval, device, os.path.dirname(ofile))  # what every product of a job knows
     summary = dict(quantiles=getattr(args, "quantiles", None), ofile=ofile, loaders=loaders, ics_per_batch=max(1, int(args.batch) // members))
-    own = {Summary: summary, Events: dict(specs=getattr(args, "events", None), file=getattr(args, "events_file", None))}
+    own = {Summary: summary, Events: dict(specs=getattr(args, "events", None), file=getattr(args, "events_file", None)),
+           LeadWindows: dict(specs=getattr(args, "lead_windows", None))}
     return [c(*job, **own.get(c, {})) for c in product_types(args)]
 
 
